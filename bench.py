@@ -11,10 +11,10 @@ Inputs (stream, codes, job table) are resident in HBM before the timed region; t
 value = channels*taps*epochs*blocks / time, whole job.  One step is ~0.25 s of GPU time: the driver's K = 20 steps keep the GPU busy for ~5 s,
 long enough for its SMI samples to see it.  At N = 1 the blocks alternate over `--launches-in-flight` (2) correlator banks, each with a HIP stream of
 its own: consecutive blocks are independent jobs, so the start of one launch fills the drain of the previous one and the gap between two launches of one
-stream (172 -> 160 us per block, profiles/ab/r06/session30.txt); `value_single_stream` is one launch after the other on one stream, as `value` was until round 6,
+stream (172 -> 160 us per block, profiles/ab/r06/session30.txt); `value_single_stream` (--full) is one launch after the other on one stream, as `value` was until round 6,
 and roofline.kernel_ms is one launch alone.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1: launched by torch.distributed.run, one rank per GPU; every rank tracks its own 32 channels of the same
   stream (weak scaling).  Every block is replicated from the ingest GPU (rank 0) to the others in the front-end's 8-bit format by the
   engine itself -- gsh_stream_group_* (csrc/stream_group.hip: RCCL broadcast, or scatter + all-gather across all xGMI links with
@@ -22,13 +22,16 @@ and roofline.kernel_ms is one launch alone.
   ordered by events per sample range, so block k + 1 travels while block k is correlated.  All of that IS inside the timed region.
   torch.distributed only hands the 128-byte communicator id round and provides the barrier / MAX-reduce of the contract -- no data.
 
-One JSON line on stdout (rank 0).  Besides the contract keys it carries
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times the K steps and prints the contract keys (metric, value, unit, higher_is_better,
+dtype, ms_per_step = milliseconds of one timed step) with the workload's configuration; --dump-outputs DIR also writes what the timed path computed in its
+last step (see --help).  With --full the line carries besides
+  spot_check    -- 4 jobs of the last launch (every rank, every bank) against the float64 oracle
   roofline      -- dominant kernel (mcorr_kernel<3,0,false,false,false,true>: E/P/L, whole-code table, paired taps) against the roofline that BINDS it:
                    vector-ALU issue (bound "valu": SURVEY 8(d)'s algorithmic flops over the dense FP32 peak, frac <= 1); the contract's byte rate
                    (8N+8T per job over the HBM peak -- a rate above 1 because 32 channels share one stream) sits in roofline.contract_hbm;
                    duration from HIP events on the launch stream
   dropin        -- what a receiver gets through the reference's own seam: 32 dll_pll_veml_tracking_hip blocks, one thread each, ONE stream, ONE
-                   Hip_Tracking_Runtime (tests/host/test_tracking_adapters bench): channel-periods/s through general_work, windows checked
+                   Hip_Tracking_Runtime (oracle/_ref/test_tracking_adapters bench): channel-periods/s through general_work, windows checked
                    against 32 reference blocks
   cpu_baseline  -- the reference's own Cpu_Multicorrelator_Real_Codes (oracle/_ref, x86 SIMD protokernels) timed on
                    this box's host cores over a bounded sample (falls back to the C port when _ref is absent)
@@ -67,7 +70,7 @@ def parse():
     ap.add_argument("--launches-in-flight", type=int, default=2,
                     help="N = 1: blocks alternate over this many correlator banks, each on a stream of its own (2: the start of one launch fills the drain of the "
                          "other and the gap between two launches of one stream, profiles/ab/r06/session30.txt); 1: one bank, one stream, as until round 6.  "
-                         "value_single_stream is reported either way")
+                         "value_single_stream is reported either way with --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-acq", action="store_true")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in leg (32 tracking blocks through general_work)")
@@ -75,7 +78,17 @@ def parse():
     ap.add_argument("--no-other-configs", action="store_true", help="skip the config 4 / config 5 figures (profiles/run_profiles.sh: keeps the "
                     "per-kernel averages of the trace about the headline workload only)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline leg")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other figure and check: the single-stream timing, the roofline (kernel alone), the spot check against the "
+                         "oracle, the HBM probe, the N > 1 sharded legs, acquisition, closed loop, other configs, PCIe, RCCL, drop-in, CPU baseline (the --no-* "
+                         "options still apply).  Off: set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what every correlator bank returned for its last launch (of the last step when "
+                         "--blocks-per-step >= the number of banks) to DIR/correlator_outputs.npy: float32 [banks, channels x epochs jobs, taps, 2 (re, im)]")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
 
 
 def make_stream_torch(torch, dev, n_samples, fs, n_sig=8, cn0=45.0):
@@ -685,13 +698,13 @@ def mcorr16_metric(dev_index, channels=32, epochs=400, n=25000):
 def dropin_metric(channels, fs, periods, periods_per_call=20, seconds=0.0):
     """What a receiver gets through the reference's own seam (north_star: "drops into a Channel unchanged"): `channels` dll_pll_veml_tracking_hip
     blocks behind their TrackingInterface adapters, one scheduler thread each as in a flowgraph (gnss_flowgraph.cc:1227-1231), ONE 25 Msps stream,
-    ONE Hip_Tracking_Runtime whose launches advance every channel that has samples.  The C++ program (tests/host/test_tracking_adapters bench,
-    compiled against the reference's headers where /root/reference is present; the binary travels with the tree) drives general_work, times the
+    ONE Hip_Tracking_Runtime whose launches advance every channel that has samples.  The C++ program (oracle/_ref/test_tracking_adapters bench,
+    compiled against the reference's headers where the reference tree is present; the binary travels with oracle/_ref/) drives general_work, times the
     threads, and checks every block's window positions against the reference's own block over the same stream."""
     import subprocess
-    exe = os.path.join(ROOT, "tests", "host", "test_tracking_adapters")
+    exe = os.path.join(ROOT, "oracle", "_ref", "test_tracking_adapters")
     if not os.path.exists(exe):
-        return {"error": "tests/host/test_tracking_adapters was not prebuilt (needs /root/reference at build time)"}
+        return {"error": "oracle/_ref/test_tracking_adapters was not prebuilt (needs the reference tree at build time)"}
     # seconds > 0: a 2 400-period stream replayed seamlessly for that long (the steady window then lasts seconds, not tens of milliseconds); periods = the cap
     r = subprocess.run([exe, "bench", str(channels), str(int(fs)), str(periods), str(periods_per_call)] + ([f"{seconds:g}"] if seconds > 0 else []), capture_output=True,
                        text=True, timeout=900, cwd="/tmp")
@@ -821,6 +834,60 @@ def bench_summary(res):
     return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in s.items()}
 
 
+def dump_outputs(path, banks, taps):
+    """--dump-outputs: what a caller of the timed path receives -- every bank's correlator outputs of its last launch, float32 [banks, jobs, taps,
+    2 (re, im)] in path/correlator_outputs.npy.  With --blocks-per-step at least the number of banks (1 400 over 2 by default) these are the last
+    launches of the last timed step; with fewer, a bank's last launch may belong to an earlier step."""
+    os.makedirs(path, exist_ok=True)
+    out = np.stack([b.read_outputs()[:, :taps] for b in banks])
+    np.save(os.path.join(path, "correlator_outputs.npy"), np.ascontiguousarray(out).view(np.float32).reshape(out.shape + (2,)))
+
+
+def spot_check(torch, cp, bank, more_banks, rows, rank, C, T, x, NB, block, last_launch, ring, raw_src, grouped):
+    """--full: a few jobs of every bank's last launch against the float64 oracle, on every rank (not timed)."""
+    import oracle
+    from gnss_sdr_amd.sharding import weak_channel_prn
+    from helpers import oracle_job, scale_err
+    out = bank.read_outputs()
+    if not grouped:
+        # time_launches() re-ran the last launch: the block the final step ended on
+        base_last = last_launch % NB * block
+        xh = x[base_last:base_last + block].cpu().numpy()
+    else:
+        # the ring holds the 8-bit block converted back to float: that is what the kernel correlated.  Only rank 0 made the block; every other rank checks
+        # what REACHED ITS RING through the group (its own copy read back from its own HBM) -- a wrong chunk offset anywhere shows here
+        lo_r, hi_r = ring.range()
+        xh = np.concatenate([ring.read(hi_r - block + k, min(1 << 20, block - k)) for k in range(0, block, 1 << 20)])
+        if rank == 0:
+            want = raw_src.to(torch.float32).reshape(-1, 2).cpu().numpy()
+            if not np.array_equal(xh.view(np.float32).reshape(-1, 2), want):
+                raise SystemExit("bench: rank 0's ring does not hold the block it pushed")
+    worst = 0.0
+    for j in (0, 1, C + 3, len(rows) - 1):
+        o32, t64, sabs = oracle_job(oracle.ca_code(weak_channel_prn(rank, C, rows[j]["code_slot"])), xh, rows[j])
+        err = scale_err(out[j, :T], t64, sabs)
+        if not np.all(err <= 1e-6):
+            raise SystemExit(f"bench: rank {rank}: GPU result of job {j} disagrees with the oracle: {out[j, :T]} vs {t64}")
+        worst = max(worst, float(np.max(err)))
+    for b2 in more_banks:
+        # the other banks computed too: three jobs of their last launch against the oracle (the ring's blocks are copies of one block, so whichever block
+        # a bank ended on, xh holds its samples)
+        out2 = b2.read_outputs()
+        for j in (0, C + 3, len(rows) - 1):
+            o32, t64, sabs = oracle_job(oracle.ca_code(weak_channel_prn(rank, C, rows[j]["code_slot"])), xh, rows[j])
+            err = scale_err(out2[j, :T], t64, sabs)
+            if not np.all(err <= 1e-6):
+                raise SystemExit(f"bench: rank {rank}: job {j} of a second bank disagrees with the oracle: {out2[j, :T]} vs {t64}")
+            worst = max(worst, float(np.max(err)))
+    if grouped:
+        # every rank's ring must hold the same block: a checksum of checksums over the ranks
+        crc = float(int(np.frombuffer(xh.tobytes(), dtype=np.uint32).sum(dtype=np.uint64)) % (1 << 40))
+        if not cp.same_everywhere(crc):
+            raise SystemExit(f"bench: rank {rank}: the replicated block differs between the ranks")
+    return {"ranks_checked": int(round(cp.reduce_sum(1.0))), "jobs_per_rank": 4, "worst_err": cp.reduce_max(worst), "bar": 1e-6,
+            "what": "|gpu - float64 truth| / sum|x| of 4 jobs of the last launch on EVERY rank" + (", each against its own ring's copy of the replicated block" if grouped else "")}
+
+
 def load_pmc():
     """profiles/pmc_r02.json: per-launch counter averages of the dominant kernels under this very command (profiles/run_profiles_r02.sh +
     profiles/summarize_r02.py; rocprofv3 --pmc passes, kernel-trace only).  None when absent."""
@@ -934,7 +1001,6 @@ def main():
     import gnss_sdr_amd
     from gnss_sdr_amd.tracking import CorrelatorBank
     from gnss_sdr_amd.codes import gps_l1_ca_code
-    import oracle  # the checker (spot check below) and the CPU baseline only; nothing the GPU legs consume comes from it
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the HIP engine has no CPU fallback)")
@@ -1045,9 +1111,12 @@ def main():
         dt = time.perf_counter() - t0
     reduce_max, reduce_sum = cp.reduce_max, cp.reduce_sum
     dt = reduce_max(dt)
+    if a.dump_outputs and rank == 0:
+        # before anything else launches on the banks: each one still holds its last launch of the last timed step
+        dump_outputs(a.dump_outputs, [bank] + more_banks, T)
     # the same steps with ONE launch at a time on one stream (what `value` was until round 6), over a fifth of the steps
     dt_single, steps_single = None, 0
-    if not grouped and more_banks:
+    if a.full and not grouped and more_banks:
         steps_single = max(2, a.steps // 5)
         k0 = a.settle_steps + a.warmup + a.steps
         with torch.cuda.stream(cs):
@@ -1062,58 +1131,19 @@ def main():
     else:
         last_launch = (max(a.settle_steps, 0) + a.warmup + a.steps) * BPS - 1
 
-    # ---- roofline of the dominant kernel: HIP events on the launch stream, inputs resident; taken straight after the timed region,
-    # before the host-side spot check lets the GPU fall idle again
-    bank.synchronize()
-    k_ms = bank.time_launches(100)
-
-    # ---- spot-check against the oracle (not timed): a few jobs of the last launch
-    out = bank.read_outputs()
-    from helpers import oracle_job, scale_err
-    if not grouped:
-        # time_launches() re-ran the last launch: the block the final step ended on
-        base_last = last_launch % NB * block
-        xh = x[base_last:base_last + block].cpu().numpy()
-    else:
-        # the ring holds the 8-bit block converted back to float: that is what the kernel correlated.  Only rank 0 made the block; every other rank checks
-        # what REACHED ITS RING through the group (its own copy read back from its own HBM) -- a wrong chunk offset anywhere shows here
-        lo_r, hi_r = ring.range()
-        xh = np.concatenate([ring.read(hi_r - block + k, min(1 << 20, block - k)) for k in range(0, block, 1 << 20)])
-        if rank == 0:
-            want = raw_src.to(torch.float32).reshape(-1, 2).cpu().numpy()
-            if not np.array_equal(xh.view(np.float32).reshape(-1, 2), want):
-                raise SystemExit("bench: rank 0's ring does not hold the block it pushed")
-    worst = 0.0
-    for j in (0, 1, C + 3, len(rows) - 1):
-        o32, t64, sabs = oracle_job(oracle.ca_code(weak_channel_prn(rank, C, rows[j]["code_slot"])), xh, rows[j])
-        err = scale_err(out[j, :T], t64, sabs)
-        if not np.all(err <= 1e-6):
-            raise SystemExit(f"bench: rank {rank}: GPU result of job {j} disagrees with the oracle: {out[j, :T]} vs {t64}")
-        worst = max(worst, float(np.max(err)))
-    for b2 in more_banks:
-        # the other banks computed too: three jobs of their last launch against the oracle (the ring's blocks are copies of one block, so whichever block
-        # a bank ended on, xh holds its samples)
-        out2 = b2.read_outputs()
-        for j in (0, C + 3, len(rows) - 1):
-            o32, t64, sabs = oracle_job(oracle.ca_code(weak_channel_prn(rank, C, rows[j]["code_slot"])), xh, rows[j])
-            err = scale_err(out2[j, :T], t64, sabs)
-            if not np.all(err <= 1e-6):
-                raise SystemExit(f"bench: rank {rank}: job {j} of a second bank disagrees with the oracle: {out2[j, :T]} vs {t64}")
-            worst = max(worst, float(np.max(err)))
-    if grouped:
-        # every rank's ring must hold the same block: a checksum of checksums over the ranks
-        crc = float(int(np.frombuffer(xh.tobytes(), dtype=np.uint32).sum(dtype=np.uint64)) % (1 << 40))
-        if not cp.same_everywhere(crc):
-            raise SystemExit(f"bench: rank {rank}: the replicated block differs between the ranks")
-    spot = {"ranks_checked": int(round(reduce_sum(1.0))), "jobs_per_rank": 4, "worst_err": reduce_max(worst), "bar": 1e-6,
-            "what": "|gpu - float64 truth| / sum|x| of 4 jobs of the last launch on EVERY rank" + (", each against its own ring's copy of the replicated block" if grouped else "")}
-
-    sharded = None
-    if grouped:
-        # the closed loop and the acquisition on the replicated stream (every rank takes part; see sharded_legs)
-        sharded = sharded_legs(torch, cp, dev, local, rank, world, ring, block, fs, n, C)
+    k_ms = spot = sharded = None
+    if a.full:
+        # ---- roofline of the dominant kernel: HIP events on the launch stream, inputs resident; taken straight after the timed region,
+        # before the host-side spot check lets the GPU fall idle again
+        bank.synchronize()
+        k_ms = bank.time_launches(100)
+        # ---- spot-check against the oracle (not timed): a few jobs of the last launch
+        spot = spot_check(torch, cp, bank, more_banks, rows, rank, C, T, x, NB, block, last_launch, ring, raw_src, grouped)
+        if grouped:
+            # the closed loop and the acquisition on the replicated stream (every rank takes part; see sharded_legs)
+            sharded = sharded_legs(torch, cp, dev, local, rank, world, ring, block, fs, n, C)
     if rank == 0:
-        pmc = load_pmc()
+        pmc = load_pmc() if a.full else None
         total_corr = float(C) * T * E * BPS * a.steps * world
         res = {
             "metric": "correlators/s",
@@ -1137,94 +1167,98 @@ def main():
                        "timed_region_s": dt,
                        "parallelism": f"channels sharded over {world} GPU(s)" + (f", every 8-bit stream block replicated by the engine's RCCL stream group "
                                       f"({os.environ.get('GSH_BENCH_DIST', 'broadcast')}), converted into every GPU's ring, overlapped with the correlation" if grouped else "")},
-            "roofline": tracking_roofline(C, E, T, n, k_ms, pmc),
-            "kernel_only_value": float(C) * T * E / (k_ms * 1e-3),
-            # `value` = blocks alternating over launches_in_flight banks and streams; value_single_stream = one launch after the other on one stream (what
-            # `value` was until round 6), timed straight after over a fifth of the steps; roofline.kernel_ms = one launch alone (HIP events, one stream)
+            # `value` = blocks alternating over launches_in_flight banks and streams; with --full, value_single_stream = one launch after the other on one stream
+            # (what `value` was until round 6), timed straight after over a fifth of the steps; roofline.kernel_ms = one launch alone (HIP events, one stream)
             "launches_in_flight": 1 + len(more_banks),
-            "value_single_stream": (float(C) * T * E * BPS * steps_single / dt_single) if dt_single else None,
-            "ms_per_step_single_stream": (dt_single / steps_single * 1e3) if dt_single else None,
             # the stream group under the launches (N > 1: RCCL over xGMI inside the engine; N = 1: no group, the block is resident)
             "rccl_ranks": G.rccl_info()["ranks"] if G is not None else 0,
             "stream_group_mode": os.environ.get("GSH_BENCH_DIST", "broadcast") if grouped else None,
-            "spot_check": spot,
         }
+        if a.full:
+            res.update({
+                "roofline": tracking_roofline(C, E, T, n, k_ms, pmc),
+                "kernel_only_value": float(C) * T * E / (k_ms * 1e-3),
+                "value_single_stream": (float(C) * T * E * BPS * steps_single / dt_single) if dt_single else None,
+                "ms_per_step_single_stream": (dt_single / steps_single * 1e3) if dt_single else None,
+                "spot_check": spot,
+            })
         if G is not None and res["rccl_ranks"] > 0:
             from gnss_sdr_amd.sample_stream import StreamGroup
             res["rccl_library"] = StreamGroup.library()
             res["rccl_library_is_test_stub"] = G.rccl_info()["version"] == 99999   # tests/host/fake_rccl.cc: a functional self-test, its rates mean nothing
             res["rccl_calls"] = G.rccl_info()["collectives"]
-        # the figures a reader needs first, as top-level scalars (the nested objects explain them)
-        rf = res["roofline"]
-        res["traffic_source"] = rf.get("traffic_source")
-        res["contract_hbm_rate_over_peak"] = rf["contract_hbm"]["rate_over_peak"]   # SURVEY 8(d) bytes / time / 8 TB/s: a RATE (> 1: 32 channels share one stream)
-        res["hbm_unique_frac"] = rf["hbm_unique"]["frac"]                            # bytes that must leave HBM once per launch / time / 8 TB/s: the utilisation
-        res["valu_issue_frac"] = rf.get("valu_issue_frac")                           # what binds the kernel (static counters)
-        try:
-            import ctypes
-            gbs = ctypes.c_double(0.0)
-            from gnss_sdr_amd import _lib as _gl
-            _gl.check(_gl.load().gsh_probe_read_bandwidth(local, 2 << 30, 8, ctypes.byref(gbs)))
-            res["hbm_read_probe_GBs"] = gbs.value        # measured streaming read of 2 GiB (> Infinity Cache) with 16-byte loads, this device, this run
-            res["hbm_read_probe_frac_of_nominal"] = gbs.value / HBM_PEAK_GBS
-            res["contract_hbm_rate_over_measured"] = rf["contract_hbm"]["achieved"] / gbs.value
-            res["hbm_unique_frac_of_measured"] = rf["hbm_unique"]["achieved_GBs"] / gbs.value
-        except Exception as e:
-            res["hbm_read_probe_GBs"] = None
-            res["hbm_read_probe_error"] = str(e)
-        if sharded is not None:
-            res.update(sharded)
-        # ---- the other GPU legs first, while the device is still at its working clocks (the CPU legs below leave it idle for ~40 s; what runs after
-        # them starts from the idle power state however long its own warm-up is)
-        if world == 1 and not a.no_acq and not grouped:
+        if a.full:
+            # the figures a reader needs first, as top-level scalars (the nested objects explain them)
+            rf = res["roofline"]
+            res["traffic_source"] = rf.get("traffic_source")
+            res["contract_hbm_rate_over_peak"] = rf["contract_hbm"]["rate_over_peak"]   # SURVEY 8(d) bytes / time / 8 TB/s: a RATE (> 1: 32 channels share one stream)
+            res["hbm_unique_frac"] = rf["hbm_unique"]["frac"]                            # bytes that must leave HBM once per launch / time / 8 TB/s: the utilisation
+            res["valu_issue_frac"] = rf.get("valu_issue_frac")                           # what binds the kernel (static counters)
             try:
-                res["acquisition"] = acquisition_metric(torch, local, x0[:n].contiguous(), fs, pmc)
+                import ctypes
+                gbs = ctypes.c_double(0.0)
+                from gnss_sdr_amd import _lib as _gl
+                _gl.check(_gl.load().gsh_probe_read_bandwidth(local, 2 << 30, 8, ctypes.byref(gbs)))
+                res["hbm_read_probe_GBs"] = gbs.value        # measured streaming read of 2 GiB (> Infinity Cache) with 16-byte loads, this device, this run
+                res["hbm_read_probe_frac_of_nominal"] = gbs.value / HBM_PEAK_GBS
+                res["contract_hbm_rate_over_measured"] = rf["contract_hbm"]["achieved"] / gbs.value
+                res["hbm_unique_frac_of_measured"] = rf["hbm_unique"]["achieved_GBs"] / gbs.value
             except Exception as e:
-                res["acquisition"] = {"error": str(e)}
-            try:
-                res["closed_loop"] = closed_loop_metric(local, x0, block, fs, n, dop, cph, channels=C, epochs=min(E - 2, 200))
-                # ... with the lock detectors on (what the tracking adapters run), launched and as one live residency
-                res["closed_loop_lock_detectors"] = closed_loop_metric(local, x0, block, fs, n, dop, cph, channels=C, epochs=min(E - 2, 200), lock_detectors=True, live=True)
-                # one compute unit per channel: 32 channels use an eighth of the chip, 256 (BASELINE config 5's channel count) fill it
-                res["closed_loop_256ch"] = closed_loop_metric(local, x0, block, fs, n, dop, cph, channels=256, epochs=min(E - 2, 200))
-            except Exception as e:
-                res["closed_loop"] = {"error": str(e)}
-            try:
-                res["closed_loop_config4"] = closed_loop_config4_metric(torch, local)
-            except Exception as e:
-                res["closed_loop_config4"] = {"error": str(e)}
-            # the same two shapes with cooperating work-groups (gsh_trk_set_split: an option -- sums in another order, records equal to rounding): where the
-            # channels leave most of the chip idle and a window is long, several compute units share every window of a channel
-            try:
-                res["closed_loop_cooperating"] = {
-                    "config2_2_work_groups": closed_loop_metric(local, x0, block, fs, n, dop, cph, channels=C, epochs=min(E - 2, 200), lock_detectors=True, split=2),
-                    "config4_4_work_groups": closed_loop_config4_metric(torch, local, split=4)}
-            except Exception as e:
-                res["closed_loop_cooperating"] = {"error": str(e)}
-            if not a.no_other_configs:
+                res["hbm_read_probe_GBs"] = None
+                res["hbm_read_probe_error"] = str(e)
+            if sharded is not None:
+                res.update(sharded)
+            # ---- the other GPU legs first, while the device is still at its working clocks (the CPU legs below leave it idle for ~40 s; what runs after
+            # them starts from the idle power state however long its own warm-up is)
+            if world == 1 and not a.no_acq and not grouped:
                 try:
-                    res["other_configs"] = other_configs_metric(local)
+                    res["acquisition"] = acquisition_metric(torch, local, x0[:n].contiguous(), fs, pmc)
                 except Exception as e:
-                    res["other_configs"] = {"error": str(e)}
-            try:
-                res["pcie_inclusive"] = pcie_inclusive_metric(torch, local, x0, jobs, C, E, T, block)
-            except Exception as e:
-                res["pcie_inclusive"] = {"error": str(e)}
-            try:
-                res["rccl_one_rank"] = rccl_one_rank_metric(torch, local, x0, block)
-            except Exception as e:
-                res["rccl_one_rank"] = {"error": str(e)}
-        # ---- then the legs with a CPU part: the drop-in seam (32 block threads + 32 reference blocks as the checker) and the CPU baseline
-        if world == 1 and not a.no_dropin and not grouped:
-            try:
-                # the reference's cadence (one code period per general_work call, trk.cc:1898-2001) and 20 periods per call, each over a steady window of seconds
-                res["dropin"] = dropin_metric(C, fs, 4000000, 20, a.dropin_seconds)
-                res["dropin"]["one_period_per_call"] = dropin_metric(C, fs, 4000000, 1, a.dropin_seconds)
-            except Exception as e:
-                res["dropin"] = {"error": str(e)}
-        if world == 1 and not a.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(C, n, fs, T, a.cpu_seconds)
-        res["summary"] = bench_summary(res)
+                    res["acquisition"] = {"error": str(e)}
+                try:
+                    res["closed_loop"] = closed_loop_metric(local, x0, block, fs, n, dop, cph, channels=C, epochs=min(E - 2, 200))
+                    # ... with the lock detectors on (what the tracking adapters run), launched and as one live residency
+                    res["closed_loop_lock_detectors"] = closed_loop_metric(local, x0, block, fs, n, dop, cph, channels=C, epochs=min(E - 2, 200), lock_detectors=True, live=True)
+                    # one compute unit per channel: 32 channels use an eighth of the chip, 256 (BASELINE config 5's channel count) fill it
+                    res["closed_loop_256ch"] = closed_loop_metric(local, x0, block, fs, n, dop, cph, channels=256, epochs=min(E - 2, 200))
+                except Exception as e:
+                    res["closed_loop"] = {"error": str(e)}
+                try:
+                    res["closed_loop_config4"] = closed_loop_config4_metric(torch, local)
+                except Exception as e:
+                    res["closed_loop_config4"] = {"error": str(e)}
+                # the same two shapes with cooperating work-groups (gsh_trk_set_split: an option -- sums in another order, records equal to rounding): where the
+                # channels leave most of the chip idle and a window is long, several compute units share every window of a channel
+                try:
+                    res["closed_loop_cooperating"] = {
+                        "config2_2_work_groups": closed_loop_metric(local, x0, block, fs, n, dop, cph, channels=C, epochs=min(E - 2, 200), lock_detectors=True, split=2),
+                        "config4_4_work_groups": closed_loop_config4_metric(torch, local, split=4)}
+                except Exception as e:
+                    res["closed_loop_cooperating"] = {"error": str(e)}
+                if not a.no_other_configs:
+                    try:
+                        res["other_configs"] = other_configs_metric(local)
+                    except Exception as e:
+                        res["other_configs"] = {"error": str(e)}
+                try:
+                    res["pcie_inclusive"] = pcie_inclusive_metric(torch, local, x0, jobs, C, E, T, block)
+                except Exception as e:
+                    res["pcie_inclusive"] = {"error": str(e)}
+                try:
+                    res["rccl_one_rank"] = rccl_one_rank_metric(torch, local, x0, block)
+                except Exception as e:
+                    res["rccl_one_rank"] = {"error": str(e)}
+            # ---- then the legs with a CPU part: the drop-in seam (32 block threads + 32 reference blocks as the checker) and the CPU baseline
+            if world == 1 and not a.no_dropin and not grouped:
+                try:
+                    # the reference's cadence (one code period per general_work call, trk.cc:1898-2001) and 20 periods per call, each over a steady window of seconds
+                    res["dropin"] = dropin_metric(C, fs, 4000000, 20, a.dropin_seconds)
+                    res["dropin"]["one_period_per_call"] = dropin_metric(C, fs, 4000000, 1, a.dropin_seconds)
+                except Exception as e:
+                    res["dropin"] = {"error": str(e)}
+            if world == 1 and not a.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline(C, n, fs, T, a.cpu_seconds)
+            res["summary"] = bench_summary(res)
         the_line.line(json.dumps(res))
     bank.close()
     for b2 in more_banks:

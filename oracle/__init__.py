@@ -4,8 +4,9 @@
 ``oracle.ref()``  -> _ref/libgnsssdr_ref.so, the REFERENCE's own sources compiled from
                      /root/reference by oracle/Makefile (None when it was never built).
 
-Only tests/, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import
-this package.  The product (``gnss-sdr_amd/``) never does.
+Only tests/, ``__graft_entry__`` (``smoke()``, and ``oracle.ref_programs`` while it builds the test programs
+of _ref/) and ``bench.py``'s ``--full`` legs (spot check, CPU baselines) may import this package.  The product
+(``gnss-sdr_amd/``) never does.
 """
 from __future__ import annotations
 

@@ -1,4 +1,6 @@
 #!/bin/bash
+# NOTE: a record of an earlier profiling visit.  It predates bench.py --full (roofline, acquisition and the other secondary legs now need it) and the
+# move of the reference-built test programs from tests/host/ to oracle/_ref/: adjust both before running it again.
 # Run ON THE GPU BOX (through gpurun) from the repo root:  bash profiles/run_profiles_r02.sh <tag>
 # rocprofv3 passes over the SAME bench.py command (shortened: fewer steps, no CPU leg), kernel-trace only in every --pmc pass, as
 # /opt/skills/guides/MI355X_MICROARCH.md prescribes:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The fake-engine program of tests/test_tracking_adapters.py (adapters + block + Hip_Tracking_Runtime + Hip_Sample_Ring in front of tests/host/fake_gsh_engine.cc)
 rebuilt with -fsanitize=thread and run: thirteen signals, restarts, the dump / TOW cases and 32 block threads on one shared runtime, with one device handle for all
-of them and with four channels per handle (eight groups).  Needs /root/reference (the adapters compile against its headers); about three minutes.
+of them and with four channels per handle (eight groups).  Needs the reference tree (the adapters compile against its headers); about three minutes.
 
 Then tests/host/test_channel.cc the same way: the reference's own Channel / ChannelFsm / channel_msg_receiver_cc over the HIP adapters -- a channel's whole life, twelve
 channels with four of them churning, seven kinds of injected engine failure (the reference's own lock-order inversion is suppressed: tests/host/tsan_reference.supp).
@@ -16,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as g  # noqa: E402
 
-out = "/tmp/test_tracking_adapters_tsan"
+# beside the program it is relinked from: its run paths ($ORIGIN) find the libraries from there only
+out = os.path.join(ROOT, "oracle", "_ref", "test_tracking_adapters_tsan")
 real, cmds = subprocess.run, []
 
 
@@ -47,7 +48,7 @@ for per_handle in ("", "4"):
 # ---- the reference's Channel over the HIP adapters (tests/host/test_channel.cc): channel life, churn and the injected engine failures under ThreadSanitizer
 chan = g.build_channel_test(tsan=True)
 if not chan:
-    sys.exit("tests/host/test_channel_fake_tsan was not built (no /root/reference here?)")
+    sys.exit("oracle/_ref/test_channel_fake_tsan was not built (no reference tree here?)")
 env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 suppressions=" + os.path.join(ROOT, "tests", "host", "tsan_reference.supp"))
 r = real([chan, "all"], capture_output=True, text=True, cwd="/tmp", env=env, timeout=1800)
 reports = (r.stdout + r.stderr).count("WARNING: ThreadSanitizer")

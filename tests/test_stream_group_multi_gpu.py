@@ -333,7 +333,7 @@ def test_bench_gpus_2_spawns_its_ranks_and_shards(devices, dist_mode):
         env.update(GSH_BENCH_SHARE_GPU="1", GSH_BENCH_BACKEND="gloo")
     env["GSH_BENCH_DIST"] = dist_mode
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--settle-steps", "0", "--blocks-per-step", "3",
-                        "--epochs", "40"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--epochs", "40", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -1,7 +1,7 @@
-"""tests/host/test_tracking_adapters: the TrackingInterface adapters (GPS_L1_CA_DLL_PLL_Tracking_HIP, Galileo_E1_DLL_PLL_VEML_Tracking_HIP,
+"""oracle/_ref/test_tracking_adapters: the TrackingInterface adapters (GPS_L1_CA_DLL_PLL_Tracking_HIP, Galileo_E1_DLL_PLL_VEML_Tracking_HIP,
 GPS_L5_DLL_PLL_Tracking_HIP, Galileo_E5a_DLL_PLL_Tracking_HIP), the dll_pll_veml_tracking_hip GNU Radio block and the Dll_Pll_Conf ->
 gsh_trk_conf mapper, compiled against the reference's own headers and checked against the reference's own tracking chain
-(oracle/_ref/libgnsssdr_ref_trk.so).  The binary is built by __graft_entry__.build() where /root/reference is present and travels with the tree.
+(oracle/_ref/libgnsssdr_ref_trk.so).  The binary is built by __graft_entry__.build() where the reference tree is present and travels with oracle/_ref/.
 
 CPU: `conf` mode -- the mapper equals what dll_pll_veml_tracking's constructor derives, field by field, and the local replicas equal the block's.
 GPU: both chains driven through general_work over the same stream, call for call (window positions, symbol timing, Prompt_I, Doppler, C/N0,
@@ -12,14 +12,14 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "host", "test_tracking_adapters")
+BIN = os.path.join(ROOT, "oracle", "_ref", "test_tracking_adapters")
 
 
 def _bin():
     if not os.path.exists(BIN):
         import __graft_entry__ as g
         if not g.build_tracking_adapter_test():
-            pytest.skip("tests/host/test_tracking_adapters was not prebuilt and /root/reference is not present here")
+            pytest.skip("oracle/_ref/test_tracking_adapters was not prebuilt and the reference tree is not present here")
     return BIN
 
 
@@ -39,7 +39,7 @@ def test_block_and_runtime_against_the_fake_engine(launch_ahead, channels_per_ha
     channels per device handle, so that the 32 blocks of the shared stream sit in eight groups with launches, and wake-ups, of their own."""
     fake = _bin() + "_fake"
     if not os.path.exists(fake):
-        pytest.skip("tests/host/test_tracking_adapters_fake was not prebuilt and /root/reference is not present here")
+        pytest.skip("oracle/_ref/test_tracking_adapters_fake was not prebuilt and the reference tree is not present here")
     r = subprocess.run([fake], capture_output=True, text=True, timeout=900, cwd="/tmp", env=dict(os.environ, GSH_TRK_LAUNCH_AHEAD=launch_ahead, **({"GSH_TEST_CHANNELS_PER_LAUNCH": channels_per_handle} if channels_per_handle else {})))
     tail = "\n".join(l for l in r.stdout.splitlines() if "FAIL" in l or "shared stream" in l or "OK" in l or "dump" in l or "restart" in l)
     print(tail[-3000:])
@@ -52,7 +52,7 @@ def test_launched_mode_against_the_fake_engine():
     configuration with <role>.hip_live=false takes."""
     fake = _bin() + "_fake"
     if not os.path.exists(fake):
-        pytest.skip("tests/host/test_tracking_adapters_fake was not prebuilt and /root/reference is not present here")
+        pytest.skip("oracle/_ref/test_tracking_adapters_fake was not prebuilt and the reference tree is not present here")
     r = subprocess.run([fake], capture_output=True, text=True, timeout=900, cwd="/tmp", env=dict(os.environ, GSH_TRK_LIVE="0"))
     assert r.returncode == 0 and "TRACKING ADAPTERS OK" in r.stdout and "FAKE ENGINE" not in r.stderr, r.stdout[-4000:] + r.stderr[-2000:]
 
@@ -65,7 +65,7 @@ def test_blocks_dealt_over_three_devices_share_one_replicated_stream():
     compared with the reference's own blocks as everywhere else."""
     fake = _bin() + "_fake"
     if not os.path.exists(fake):
-        pytest.skip("tests/host/test_tracking_adapters_fake was not prebuilt and /root/reference is not present here")
+        pytest.skip("oracle/_ref/test_tracking_adapters_fake was not prebuilt and the reference tree is not present here")
     r = subprocess.run([fake, "runtime", "32", "2400", "10"], capture_output=True, text=True, timeout=900, cwd="/tmp",
                        env=dict(os.environ, FAKE_GSH_DEVICES="3", GSH_TEST_HIP_DEVICES="0,1,2"))
     print("\n".join(l for l in r.stdout.splitlines() if "shared stream" in l or "FAIL" in l)[-2000:])
@@ -129,7 +129,7 @@ def test_tracking_adapters_in_launched_mode_with_cooperating_work_groups(gpu):
 
 
 # ---- the reference's own Channel / ChannelFsm / channel_msg_receiver_cc over the HIP adapters (tests/host/test_channel.cc, round 5) ---------------------------------------------
-CHAN = os.path.join(ROOT, "tests", "host", "test_channel")
+CHAN = os.path.join(ROOT, "oracle", "_ref", "test_channel")
 
 
 def _chan(fake):
@@ -137,7 +137,7 @@ def _chan(fake):
     if not os.path.exists(exe):
         import __graft_entry__ as g
         if not g.build_channel_test():
-            pytest.skip("tests/host/test_channel was not prebuilt and /root/reference is not present here")
+            pytest.skip("oracle/_ref/test_channel was not prebuilt and the reference tree is not present here")
     return exe
 
 
