@@ -119,6 +119,20 @@ class TrkEpoch(C.Structure):
     ]
 
 
+class PackedFormat(C.Structure):
+    """gsh_packed_format (32 bytes): packed 2-bit / 4-bit front-end samples (sample_stream.PackedFormat builds it from a signal source's properties)."""
+    _fields_ = [
+        ("family", C.c_int32),
+        ("sample_type", C.c_int32),
+        ("item_size", C.c_int32),
+        ("big_endian_bytes", C.c_int32),
+        ("big_endian_items", C.c_int32),
+        ("rf_channels", C.c_int32),
+        ("channel", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class AcqResult(C.Structure):
     """gsh_acq_result."""
     _fields_ = [
@@ -213,9 +227,17 @@ SYMBOLS = {
     "gsh_stream_range": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsh_stream_read": (C.c_int, [_P, C.c_uint64, C.c_uint64, _F]),
     "gsh_convert_samples_device": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, _P, C.c_uint64, _P]),
+    "gsh_packed_bytes": (C.c_int, [C.POINTER(PackedFormat), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gsh_unpack_device": (C.c_int, [C.c_int, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_uint64, C.c_int, _P, _P]),
+    "gsh_stream_push_packed": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "gsh_stream_push_packed_device": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, _P, C.POINTER(C.c_uint64)]),
+    "gsh_stream_push_packed_pinned_async": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "gsh_stream_group_push_packed": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "gsh_stream_group_push_packed_device": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     "gsh_fir_create": (C.c_int, [C.c_int, _F, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
     "gsh_fir_destroy": (None, [_P]),
     "gsh_fir_process_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64), _P]),
+    "gsh_fir_create_packed": (C.c_int, [C.c_int, _F, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(PackedFormat), C.POINTER(_P)]),
     "gsh_direct_resample_device": (C.c_int, [C.c_int, _P, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_uint64, _P, C.c_uint64,
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P]),
     "gsh_trk_create": (C.c_int, [C.c_int, C.POINTER(TrkConf), C.c_int, C.c_int, C.POINTER(_P)]),

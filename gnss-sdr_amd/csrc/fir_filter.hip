@@ -12,6 +12,7 @@
 // it stages the translated inputs its tile needs (tile * D + K - 1 samples) in LDS once, then every thread forms its outputs from LDS with
 // the taps read as wave-uniform LDS broadcasts.
 #include "gsh_internal.h"
+#include "packed_unpack.h"
 #include <cmath>
 #include <new>
 #include <vector>
@@ -21,7 +22,8 @@ struct gsh_fir
     int device{0};
     int n_taps{0};
     int decimation{1};
-    int in_kind{0};          // 0 complex64, 1 real float32, 2 real int16, 3 real int8 (ccf / fcf / scf with short or byte items)
+    int in_kind{0};          // 0 complex64, 1 real float32, 2 real int16, 3 real int8 (ccf / fcf / scf with short or byte items), 4 packed bytes
+    gsh::PackedCode packed{};    // in_kind 4: the packed format (gsh_fir_create_packed)
     double rev_per_sample{0.0};  // f_c / f_s
     float* d_taps{nullptr};
     float2* d_hist{nullptr};     // the last n_taps - 1 (untranslated, converted) input samples of the stream so far
@@ -51,6 +53,7 @@ struct FirArgs
     unsigned long long n_in, n_out;
     double rev_per_sample;
     int n_taps, decimation, in_kind, tile;
+    PackedCode packed;           // in_kind 4
 };
 
 __device__ __forceinline__ float2 load_item(const void* in, unsigned long long i, int kind)
@@ -68,14 +71,24 @@ __device__ __forceinline__ float2 load_item(const void* in, unsigned long long i
         }
 }
 
+// input item i of the block: PACKED (input_kind 4) decodes it with the decoder of the ring write (packed_unpack.h), so that the packed FIR sees
+// exactly the samples gsh_unpack_device yields; the other kinds keep their own instantiation of the kernels
+template <bool PACKED>
+__device__ __forceinline__ float2 load_input(const FirArgs& a, unsigned long long i)
+{
+    if (PACKED) return packed_sample(static_cast<const unsigned char*>(a.in), a.packed, i);
+    return load_item(a.in, i, a.in_kind);
+}
+
 // sample with absolute index n (may lie in the history or before the stream), translated to baseband
+template <bool PACKED>
 __device__ __forceinline__ float2 fetch_translated(const FirArgs& a, long long n)
 {
     if (n < 0) return make_float2(0.0f, 0.0f);
     float2 x;
     const long long rel = n - static_cast<long long>(a.in0);
     if (rel >= 0)
-        x = load_item(a.in, static_cast<unsigned long long>(rel), a.in_kind);
+        x = load_input<PACKED>(a, static_cast<unsigned long long>(rel));
     else
         x = a.hist[(a.n_taps - 1) + rel];  // hist[K-1-1] is sample in0 - 1
     if (a.rev_per_sample != 0.0)
@@ -89,6 +102,7 @@ __device__ __forceinline__ float2 fetch_translated(const FirArgs& a, long long n
     return x;
 }
 
+template <bool PACKED>
 __global__ __launch_bounds__(FIR_THREADS) void fir_kernel(FirArgs a)
 {
     extern __shared__ __align__(16) float2 lds[];
@@ -103,7 +117,7 @@ __global__ __launch_bounds__(FIR_THREADS) void fir_kernel(FirArgs a)
             const int span = (cnt - 1) * D + K;
             __syncthreads();
             for (int i = threadIdx.x; i < K; i += FIR_THREADS) ltaps[i] = a.taps[i];
-            for (int i = threadIdx.x; i < span; i += FIR_THREADS) lx[i] = fetch_translated(a, first + i);
+            for (int i = threadIdx.x; i < span; i += FIR_THREADS) lx[i] = fetch_translated<PACKED>(a, first + i);
             __syncthreads();
             for (int j = threadIdx.x; j < cnt; j += FIR_THREADS)
                 {
@@ -123,6 +137,7 @@ __global__ __launch_bounds__(FIR_THREADS) void fir_kernel(FirArgs a)
 }
 
 // keep the last K - 1 input samples (converted, untranslated) for the next call
+template <bool PACKED>
 __global__ void fir_history_kernel(FirArgs a)
 {
     const int K1 = a.n_taps - 1;
@@ -132,13 +147,45 @@ __global__ void fir_history_kernel(FirArgs a)
             const long long rel = static_cast<long long>(a.n_in) - K1 + i;
             float2 v;
             if (rel >= 0)
-                v = load_item(a.in, static_cast<unsigned long long>(rel), a.in_kind);
+                v = load_input<PACKED>(a, static_cast<unsigned long long>(rel));
             else
                 v = (K1 + rel >= 0) ? a.hist[K1 + rel] : make_float2(0.0f, 0.0f);
             a.hist_out[i] = v;
         }
 }
 }  // namespace
+}  // namespace gsh
+
+namespace gsh
+{
+// the handle behind gsh_fir_create / gsh_fir_create_packed (arguments checked by the caller); packed: input_kind 4
+int fir_create(int device, const float* taps, int n_taps, int decimation, double center_freq_hz, double sampling_freq_hz, int input_kind,
+    const PackedCode* packed, gsh_fir_t** out)
+{
+    int rc = use_device(device);
+    if (rc != GSH_OK) return rc;
+    gsh_fir* f = new (std::nothrow) gsh_fir();
+    GSH_REQUIRE(f != nullptr, "out of host memory");
+    f->device = device;
+    f->n_taps = n_taps;
+    f->decimation = decimation;
+    f->in_kind = input_kind;
+    if (packed != nullptr) f->packed = *packed;
+    f->rev_per_sample = center_freq_hz / sampling_freq_hz;
+    auto fail = [&](hipError_t e, const char* what) {
+        hip_fail(e, what, __FILE__, __LINE__);
+        gsh_fir_destroy(f);
+        return GSH_ERR_HIP;
+    };
+    hipError_t e;
+    if ((e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
+    if ((e = hipMalloc(&f->d_taps, sizeof(float) * n_taps)) != hipSuccess) return fail(e, "hipMalloc(taps)");
+    if ((e = hipMemcpy(f->d_taps, taps, sizeof(float) * n_taps, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy(taps)");
+    if ((e = hipMalloc(&f->d_hist, sizeof(float2) * 2 * static_cast<size_t>(n_taps))) != hipSuccess) return fail(e, "hipMalloc(hist)");
+    if ((e = hipMemset(f->d_hist, 0, sizeof(float2) * 2 * static_cast<size_t>(n_taps))) != hipSuccess) return fail(e, "hipMemset(hist)");
+    *out = f;
+    return GSH_OK;
+}
 }  // namespace gsh
 
 extern "C"
@@ -152,28 +199,21 @@ extern "C"
         GSH_REQUIRE(decimation >= 1 && decimation <= 64, "decimation %d outside 1..64", decimation);
         GSH_REQUIRE(sampling_freq_hz > 0.0, "sampling frequency must be positive");
         GSH_REQUIRE(input_kind >= 0 && input_kind <= 3, "input_kind %d outside 0..3", input_kind);
-        int rc = gsh::use_device(device);
+        return gsh::fir_create(device, taps, n_taps, decimation, center_freq_hz, sampling_freq_hz, input_kind, nullptr, out);
+    }
+
+    int gsh_fir_create_packed(int device, const float* taps, int n_taps, int decimation, double center_freq_hz, double sampling_freq_hz,
+        const gsh_packed_format* fmt, gsh_fir_t** out)
+    {
+        GSH_REQUIRE(out != nullptr && taps != nullptr, "null argument");
+        *out = nullptr;
+        GSH_REQUIRE(n_taps >= 1 && n_taps <= gsh::FIR_MAX_TAPS, "n_taps %d outside 1..%d", n_taps, gsh::FIR_MAX_TAPS);
+        GSH_REQUIRE(decimation >= 1 && decimation <= 64, "decimation %d outside 1..64", decimation);
+        GSH_REQUIRE(sampling_freq_hz > 0.0, "sampling frequency must be positive");
+        gsh::PackedCode c;
+        int rc = gsh::packed_code(fmt, &c);
         if (rc != GSH_OK) return rc;
-        gsh_fir* f = new (std::nothrow) gsh_fir();
-        GSH_REQUIRE(f != nullptr, "out of host memory");
-        f->device = device;
-        f->n_taps = n_taps;
-        f->decimation = decimation;
-        f->in_kind = input_kind;
-        f->rev_per_sample = center_freq_hz / sampling_freq_hz;
-        auto fail = [&](hipError_t e, const char* what) {
-            gsh::hip_fail(e, what, __FILE__, __LINE__);
-            gsh_fir_destroy(f);
-            return GSH_ERR_HIP;
-        };
-        hipError_t e;
-        if ((e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
-        if ((e = hipMalloc(&f->d_taps, sizeof(float) * n_taps)) != hipSuccess) return fail(e, "hipMalloc(taps)");
-        if ((e = hipMemcpy(f->d_taps, taps, sizeof(float) * n_taps, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy(taps)");
-        if ((e = hipMalloc(&f->d_hist, sizeof(float2) * 2 * static_cast<size_t>(n_taps))) != hipSuccess) return fail(e, "hipMalloc(hist)");
-        if ((e = hipMemset(f->d_hist, 0, sizeof(float2) * 2 * static_cast<size_t>(n_taps))) != hipSuccess) return fail(e, "hipMemset(hist)");
-        *out = f;
-        return GSH_OK;
+        return gsh::fir_create(device, taps, n_taps, decimation, center_freq_hz, sampling_freq_hz, 4, &c, out);
     }
 
     void gsh_fir_destroy(gsh_fir_t* f)
@@ -192,6 +232,12 @@ extern "C"
         GSH_REQUIRE(f != nullptr && n_out != nullptr, "null argument");
         *n_out = 0;
         GSH_REQUIRE(n_in == 0 || device_in != nullptr, "null input");
+        if (f->in_kind == 4)
+            {
+                unsigned long long bytes = 0;  // a packed block is whole input items (n_in samples of the format's channel)
+                int rc = gsh::packed_size(f->packed, n_in, &bytes);
+                if (rc != GSH_OK) return rc;
+            }
         GSH_HIP(hipSetDevice(f->device));
         hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : f->stream;
         // outputs m with m D < n_in_total + n_in and m >= n_out_total (output m uses inputs up to m D)
@@ -214,6 +260,7 @@ extern "C"
         a.n_taps = f->n_taps;
         a.decimation = f->decimation;
         a.in_kind = f->in_kind;
+        a.packed = f->packed;
         int tile = gsh::FIR_TILE;
         while (tile > 64 && (tile - 1) * f->decimation + f->n_taps > gsh::FIR_MAX_SPAN) tile >>= 1;
         a.tile = tile;
@@ -223,14 +270,22 @@ extern "C"
                 const size_t lds = sizeof(float2) * (span + ((f->n_taps + 1) >> 1));
                 unsigned long long blocks = (count + tile - 1) / tile;
                 if (blocks > 256ull * 8ull) blocks = 256ull * 8ull;
+                const bool packed = f->in_kind == 4;
                 if (lds > 64 * 1024)
-                    GSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gsh::fir_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-                gsh::fir_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(gsh::FIR_THREADS), lds, s>>>(a);
+                    GSH_HIP(hipFuncSetAttribute(packed ? reinterpret_cast<const void*>(gsh::fir_kernel<true>) : reinterpret_cast<const void*>(gsh::fir_kernel<false>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+                if (packed)
+                    gsh::fir_kernel<true><<<dim3(static_cast<unsigned>(blocks)), dim3(gsh::FIR_THREADS), lds, s>>>(a);
+                else
+                    gsh::fir_kernel<false><<<dim3(static_cast<unsigned>(blocks)), dim3(gsh::FIR_THREADS), lds, s>>>(a);
                 GSH_HIP(hipGetLastError());
             }
         if (n_in > 0 && f->n_taps > 1)
             {
-                gsh::fir_history_kernel<<<dim3(4), dim3(256), 0, s>>>(a);
+                if (f->in_kind == 4)
+                    gsh::fir_history_kernel<true><<<dim3(4), dim3(256), 0, s>>>(a);
+                else
+                    gsh::fir_history_kernel<false><<<dim3(4), dim3(256), 0, s>>>(a);
                 GSH_HIP(hipGetLastError());
                 // swap the halves: the new history becomes the current one (stream-ordered copy keeps the handle's pointer stable)
                 GSH_HIP(hipMemcpyAsync(f->d_hist, f->d_hist + f->n_taps, sizeof(float2) * (f->n_taps - 1), hipMemcpyDeviceToDevice, s));

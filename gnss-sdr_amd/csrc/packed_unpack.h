@@ -1,0 +1,96 @@
+// Packed 2-bit / 4-bit front-end samples (gsh_packed_format, include/gnss_sdr_hip.h): the one decoder that the ring write, the stand-alone unpack
+// (packed_unpack.hip) and the packed FIR's load_item (fir_filter.hip) share, so that every path yields the same value for sample k by construction.
+// Reference blocks restated (src/algorithms/signal_source/gnuradio_blocks/, "blocks/" below) with the GNU Radio conversion behind each (scale 1).
+#ifndef GSH_PACKED_UNPACK_H
+#define GSH_PACKED_UNPACK_H
+#include "gsh_internal.h"
+
+namespace gsh
+{
+// a validated gsh_packed_format, reduced to what the decoder needs
+struct PackedCode
+{
+    int family;       // GSH_PACKED_*
+    int cplx;         // 1: complex samples (I, Q); 0: real
+    int spb;          // samples per byte and RF channel: 4 (2-bit real), 2 (2-bit complex), 1 (4-bit complex, NTLab)
+    int item_bytes;   // bytes per input item: 2 only for big-endian short items of TWO_BIT
+    int rev;          // TWO_BIT big_endian_bytes: sample order within a byte reversed
+    int qi;           // TWO_BIT / FOUR_BIT_CPX sample_type qi
+    int channel;      // NTLab RF channel
+};
+
+// validate *fmt (GSH_ERR_INVALID with a message) and reduce it
+int packed_code(const gsh_packed_format* fmt, PackedCode* out);
+// bytes holding n samples; GSH_ERR_INVALID when n is not a whole number of input items
+int packed_size(const PackedCode& c, unsigned long long n, unsigned long long* bytes);
+// samples [first, first + n) of the packed buffer at d_src -> complex64 at d_dst (conjugated when conj), or float32 at d_dst for a real family
+int unpack_packed(const void* d_src, const PackedCode& c, unsigned long long first, unsigned long long n, int conj, void* d_dst, hipStream_t s);
+
+// a signed 2-bit field stored the reference's way -- `signed x : 2` assigned (c >> k) & 3 -- wraps in two's complement: 0, 1, -2, -1
+// (blocks/unpack_2bit_samples.cc:22-28, unpack_byte_2bit_cpx_samples.cc:26-29,80-89, unpack_byte_2bit_samples.cc:21-24,54-64)
+__host__ __device__ __forceinline__ int s2(unsigned v) { return static_cast<int>(v & 1u) - static_cast<int>(v & 2u); }
+
+// byte of the packed stream that holds sample k of the code's RF channel, and the position of the sample inside it
+__host__ __device__ __forceinline__ unsigned long long packed_byte_index(const PackedCode& c, unsigned long long k)
+{
+    const unsigned long long b = k / static_cast<unsigned>(c.spb);
+    // big_endian_items with short items: the two bytes of each item are swapped before unpacking (blocks/unpack_2bit_samples.cc:63-80,114-115,134-141)
+    return c.item_bytes == 2 ? (b ^ 1ull) : b;
+}
+
+// sample number `pos` (0 .. spb - 1) of byte `byte` as (I, Q); Q = 0 for the real families
+__host__ __device__ __forceinline__ float2 packed_decode(const PackedCode& c, unsigned byte, int pos)
+{
+    switch (c.family)
+        {
+        case GSH_PACKED_TWO_BIT:
+            {
+                // unpack_2bit_samples: 4 values per byte, field f of bits 2f+1:2f, value 2 s + 1 (blocks/unpack_2bit_samples.cc:150-206).  Order
+                // of the fields: 0 1 2 3 (:164-177); big_endian_bytes reverses it (3 2 1 0, :152-162); reverse_interleaving (qi) swaps each pair (1 0 3 2,
+                // :194-205; with big_endian_bytes 2 3 0 1, :181-191).  Real: value k is sample k (char_to_float); complex: values 2k, 2k+1 are I, Q
+                // (interleaved_char_to_complex(false), two_bit_packed_file_signal_source.cc:126-136).
+                auto value = [&](int p) {
+                    const int f = (c.rev ? 3 - p : p) ^ (c.qi ? 1 : 0);
+                    return static_cast<float>(2 * s2(byte >> (2 * f)) + 1);
+                };
+                if (!c.cplx) return make_float2(value(pos), 0.0f);
+                return make_float2(value(2 * pos), value(2 * pos + 1));
+            }
+        case GSH_PACKED_TWO_BIT_CPX:
+            {
+                // unpack_byte_2bit_cpx_samples emits bits 5:4, 7:6, 1:0, 3:2 (blocks/unpack_byte_2bit_cpx_samples.cc:77-89, its own I/Q swap);
+                // interleaved_short_to_complex(false, true) swaps every pair back (two_bit_cpx_file_signal_source.cc:75): sample 0 = (bits 7:6, bits 5:4),
+                // sample 1 = (bits 3:2, bits 1:0)
+                const int sh = pos ? 0 : 4;
+                return make_float2(static_cast<float>(2 * s2(byte >> (sh + 2)) + 1), static_cast<float>(2 * s2(byte >> sh) + 1));
+            }
+        case GSH_PACKED_FOUR_BIT_CPX:
+            {
+                // unpack_byte_4bit_samples: low nibble first, then the high one; a nibble n >= 8 maps to 2 (n - 16) + 1, else 2 n + 1
+                // (blocks/unpack_byte_4bit_samples.cc:44-64); interleaved_short_to_complex(false, qi) swaps them for qi (four_bit_cpx_file_signal_source.cc:121)
+                const unsigned lo = byte & 15u, hi = (byte >> 4) & 15u;
+                const float vlo = static_cast<float>(lo >= 8u ? 2 * (static_cast<int>(lo) - 16) + 1 : 2 * static_cast<int>(lo) + 1);
+                const float vhi = static_cast<float>(hi >= 8u ? 2 * (static_cast<int>(hi) - 16) + 1 : 2 * static_cast<int>(hi) + 1);
+                return c.qi ? make_float2(vhi, vlo) : make_float2(vlo, vhi);
+            }
+        case GSH_PACKED_NSR:
+            // unpack_byte_2bit_samples: bits 1:0, 3:2, 5:4, 7:6, the signed field itself (-2 .. 1), no 2 s + 1 (blocks/unpack_byte_2bit_samples.cc:50-64)
+            return make_float2(static_cast<float>(s2(byte >> (2 * pos))), 0.0f);
+        default:
+            {
+                // unpack_ntlab_2bit_samples with 4 channels: channel n reads bits 7-2n (magnitude) and 6-2n (sign), value S ? +mag : -mag, mag M ? 3 : 1
+                // (blocks/unpack_ntlab_2bit_samples.cc:57-77)
+                const int shift = 2 * (3 - c.channel);
+                const int mag = ((byte >> (shift + 1)) & 1u) ? 3 : 1;
+                return make_float2(static_cast<float>(((byte >> shift) & 1u) ? mag : -mag), 0.0f);
+            }
+        }
+}
+
+// sample k of the code's RF channel in the packed buffer `src` (sample 0 = the first of src[0])
+__host__ __device__ __forceinline__ float2 packed_sample(const unsigned char* src, const PackedCode& c, unsigned long long k)
+{
+    return packed_decode(c, src[packed_byte_index(c, k)], static_cast<int>(k % static_cast<unsigned>(c.spb)));
+}
+}  // namespace gsh
+#endif

@@ -3,6 +3,7 @@
 #ifndef GSH_SAMPLE_STREAM_H
 #define GSH_SAMPLE_STREAM_H
 #include "gsh_internal.h"
+#include "packed_unpack.h"
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -96,6 +97,10 @@ int stream_wait_pushed(gsh_stream* s, unsigned long long need_end, hipStream_t s
 // queue the conversion of n raw items at d_src (device memory) into ring positions [next, next + n) on the ring's own stream, after the readers'
 // fences; records `pushed` and advances `next`
 int stream_write_device_items(gsh_stream* s, const void* d_src, unsigned long long n, int item_type, int conj, hipStream_t st);
+// the same for n packed complex samples at d_src (sample 0 at its first byte)
+int stream_write_device_packed(gsh_stream* s, const void* d_src, const PackedCode& c, unsigned long long n, int conj, hipStream_t st);
+// validate a packed format for a ring (complex families only) and the byte count of n samples
+int packed_ring_format(const gsh_packed_format* fmt, unsigned long long n, PackedCode* c, unsigned long long* bytes);
 // the two live words of the ring (allocated, and published for what is resident now, at the first call); nullptr + last error on failure
 unsigned long long* stream_live_words(gsh_stream* s);
 // lowest window start any registered live channel still has to read; ~0ull when none is active

@@ -1,6 +1,7 @@
 // gsh_stream_*: the IF sample stream of one front-end as a ring in device memory, addressed by absolute sample index.
 // See include/gnss_sdr_hip.h for the contract and the reference pieces it stands in for.
 #include "sample_stream.h"
+#include "packed_unpack.h"
 #include "sample_convert.h"
 #include <algorithm>
 #include <cstdlib>
@@ -142,8 +143,10 @@ hipError_t release_buffer(gsh_stream* s, void* p, bool host)
 
 // queue the conversion of n items at d_src into ring positions of absolute indices [first, first + n) on `st`.  host_src: d_src is page-locked HOST memory
 // holding gr_complex items to be taken as they are -- the ring positions are then the destination of the DMA itself (no staging buffer, no second copy);
-// *copied_after (an event), when given, is recorded behind the last read of d_src.
-int write_items(gsh_stream* s, const void* d_src, unsigned long long n, int item_type, int conj, hipStream_t st, bool host_src = false, hipEvent_t copied_after = nullptr)
+// *copied_after (an event), when given, is recorded behind the last read of d_src.  packed: d_src holds packed complex samples of that format (item_type
+// unused), sample 0 at its first byte; a segment that starts inside a byte is unpacked from its first-sample offset.
+int write_items(gsh_stream* s, const void* d_src, unsigned long long n, int item_type, int conj, hipStream_t st, bool host_src = false, hipEvent_t copied_after = nullptr,
+    const gsh::PackedCode* packed = nullptr)
 {
     const size_t isz = gsh::item_bytes(item_type);
     if (!s->live_floors.empty())
@@ -177,6 +180,11 @@ int write_items(gsh_stream* s, const void* d_src, unsigned long long n, int item
                 {
                     GSH_HIP(hipMemcpyAsync(s->d_ring + p, src, sizeof(float2) * len, hipMemcpyHostToDevice, st));
                     if (done + len == n && copied_after != nullptr) GSH_HIP(hipEventRecord(copied_after, st));  // (before the mirror copy: that one reads the ring)
+                }
+            else if (packed != nullptr)
+                {
+                    int rc = gsh::unpack_packed(d_src, *packed, done, len, conj, s->d_ring + p, st);
+                    if (rc != GSH_OK) return rc;
                 }
             else
                 {
@@ -224,6 +232,25 @@ int stream_write_device_items(gsh_stream* s, const void* d_src, unsigned long lo
     if (rc != GSH_OK) return rc;
     s->next += n;
     return GSH_OK;
+}
+
+int stream_write_device_packed(gsh_stream* s, const void* d_src, const PackedCode& c, unsigned long long n, int conj, hipStream_t st)
+{
+    int rc = write_items(s, d_src, n, GSH_ITEM_BYTE, conj, st, false, nullptr, &c);
+    if (rc != GSH_OK) return rc;
+    rc = record_push(s, s->next + n, st);
+    if (rc != GSH_OK) return rc;
+    s->next += n;
+    return GSH_OK;
+}
+
+int packed_ring_format(const gsh_packed_format* fmt, unsigned long long n, PackedCode* c, unsigned long long* bytes)
+{
+    int rc = packed_code(fmt, c);
+    if (rc != GSH_OK) return rc;
+    GSH_REQUIRE(c->cplx, "packed family %d carries real IF samples: they reach a ring through a packed FIR (gsh_fir_create_packed, then gsh_stream_push_device)",
+        fmt->family);
+    return packed_size(*c, n, bytes);
 }
 }  // namespace gsh
 
@@ -541,6 +568,99 @@ extern "C"
             }
         GSH_HIP(hipMemcpyAsync(s->d_stage[slot], items, bytes, hipMemcpyHostToDevice, s->stream));
         int rc = write_items(s, s->d_stage[slot], n, item_type, inverted_spectrum ? 1 : 0, s->stream);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipEventRecord(s->stage_done[slot], s->stream));
+        rc = record_push(s, s->next + n, s->stream);
+        if (rc != GSH_OK) return rc;
+        s->next += n;
+        return GSH_OK;
+    }
+
+    int gsh_stream_push_packed(gsh_stream_t* s, const gsh_packed_format* fmt, const void* bytes, uint64_t n, int inverted_spectrum, uint64_t* first_index)
+    {
+        // gsh_stream_push for packed complex samples: the packed bytes cross PCIe into the raw staging buffer, the unpack writes the ring
+        GSH_REQUIRE(s != nullptr, "null stream");
+        GSH_REQUIRE(n == 0 || bytes != nullptr, "null items");
+        gsh::PackedCode c;
+        unsigned long long nbytes = 0;
+        int rc = gsh::packed_ring_format(fmt, n, &c, &nbytes);
+        if (rc != GSH_OK) return rc;
+        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
+        if (first_index) *first_index = s->next;
+        if (n == 0) return GSH_OK;
+        GSH_HIP(hipSetDevice(s->device));
+        if (nbytes > s->raw_cap)
+            {
+                if (s->d_raw) GSH_HIP(release_buffer(s, s->d_raw, false));
+                s->d_raw = nullptr;
+                s->raw_cap = 0;
+                GSH_HIP(hipMalloc(&s->d_raw, nbytes));
+                s->raw_cap = nbytes;
+            }
+        GSH_HIP(hipMemcpyAsync(s->d_raw, bytes, nbytes, hipMemcpyHostToDevice, s->stream));
+        rc = write_items(s, s->d_raw, n, GSH_ITEM_BYTE, inverted_spectrum ? 1 : 0, s->stream, false, nullptr, &c);
+        if (rc != GSH_OK) return rc;
+        rc = record_push(s, s->next + n, s->stream);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipStreamSynchronize(s->stream));
+        s->next += n;
+        return GSH_OK;
+    }
+
+    int gsh_stream_push_packed_device(gsh_stream_t* s, const gsh_packed_format* fmt, const void* device_bytes, uint64_t n, int inverted_spectrum, void* hip_stream,
+        uint64_t* first_index)
+    {
+        GSH_REQUIRE(s != nullptr, "null stream");
+        GSH_REQUIRE(n == 0 || device_bytes != nullptr, "null items");
+        gsh::PackedCode c;
+        unsigned long long nbytes = 0;
+        int rc = gsh::packed_ring_format(fmt, n, &c, &nbytes);
+        if (rc != GSH_OK) return rc;
+        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
+        if (first_index) *first_index = s->next;
+        if (n == 0) return GSH_OK;
+        GSH_HIP(hipSetDevice(s->device));
+        hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+        rc = gsh::stream_write_device_packed(s, device_bytes, c, n, inverted_spectrum ? 1 : 0, st);
+        if (rc != GSH_OK) return rc;
+        if (!hip_stream) GSH_HIP(hipStreamSynchronize(st));
+        return GSH_OK;
+    }
+
+    int gsh_stream_push_packed_pinned_async(gsh_stream_t* s, const gsh_packed_format* fmt, const void* bytes, uint64_t n, int inverted_spectrum,
+        uint64_t* first_index)
+    {
+        // gsh_stream_push_pinned_async for packed complex samples: page-locked packed bytes -> device staging (DMA) -> unpack into the ring; nothing waits here
+        GSH_REQUIRE(s != nullptr, "null stream");
+        GSH_REQUIRE(n == 0 || bytes != nullptr, "null items");
+        gsh::PackedCode c;
+        unsigned long long nbytes = 0;
+        int rc = gsh::packed_ring_format(fmt, n, &c, &nbytes);
+        if (rc != GSH_OK) return rc;
+        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
+        if (first_index) *first_index = s->next;
+        if (n == 0) return GSH_OK;
+        GSH_HIP(hipSetDevice(s->device));
+        const int slot = s->stage_next;
+        s->stage_next = (s->stage_next + 1) % gsh_stream::NSTAGE;
+        if (s->stage_done[slot] == nullptr)
+            GSH_HIP(hipEventCreateWithFlags(&s->stage_done[slot], hipEventDisableTiming));
+        else
+            GSH_HIP(hipEventSynchronize(s->stage_done[slot]));  // the unpack that read this device buffer four pushes ago
+        if (nbytes > s->stage_cap[slot])
+            {
+                if (s->h_stage[slot]) GSH_HIP(release_buffer(s, s->h_stage[slot], true));
+                if (s->d_stage[slot]) GSH_HIP(release_buffer(s, s->d_stage[slot], false));
+                s->h_stage[slot] = nullptr;
+                s->d_stage[slot] = nullptr;
+                s->stage_cap[slot] = 0;
+                const size_t cap = nbytes + nbytes / 2;
+                GSH_HIP(hipHostMalloc(&s->h_stage[slot], cap, hipHostMallocDefault));  // (kept in step with the staged path, which shares the slots)
+                GSH_HIP(hipMalloc(&s->d_stage[slot], cap));
+                s->stage_cap[slot] = cap;
+            }
+        GSH_HIP(hipMemcpyAsync(s->d_stage[slot], bytes, nbytes, hipMemcpyHostToDevice, s->stream));
+        rc = write_items(s, s->d_stage[slot], n, GSH_ITEM_BYTE, inverted_spectrum ? 1 : 0, s->stream, false, nullptr, &c);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipEventRecord(s->stage_done[slot], s->stream));
         rc = record_push(s, s->next + n, s->stream);

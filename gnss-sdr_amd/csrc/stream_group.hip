@@ -290,16 +290,25 @@ int root_local_index(const gsh_stream_group* g)
     return -1;
 }
 
-int push_common(gsh_stream_group* g, const void* items, bool items_on_device, uint64_t n, int item_type, int inverted_spectrum, uint64_t* first_index)
+// fmt: packed complex samples (gsh_stream_group_push_packed): the block is its packed bytes, every rank unpacks them into its ring
+int push_common(gsh_stream_group* g, const void* items, bool items_on_device, uint64_t n, int item_type, int inverted_spectrum, uint64_t* first_index,
+    const gsh_packed_format* fmt = nullptr)
 {
     GSH_REQUIRE(g != nullptr && !g->rings.empty(), "null group");
+    gsh::PackedCode packed{};
+    unsigned long long packed_bytes = 0;
+    if (fmt != nullptr)
+        {
+            int rc = gsh::packed_ring_format(fmt, n, &packed, &packed_bytes);
+            if (rc != GSH_OK) return rc;
+        }
     const size_t isz = gsh::item_bytes(item_type);
-    GSH_REQUIRE(isz != 0, "unknown item type %d", item_type);
+    GSH_REQUIRE(fmt != nullptr || isz != 0, "unknown item type %d", item_type);
     for (gsh_stream* s : g->rings)
         GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
     if (first_index) *first_index = g->rings[0]->next;
     if (n == 0) return GSH_OK;
-    const size_t bytes = static_cast<size_t>(n) * isz;
+    const size_t bytes = fmt != nullptr ? static_cast<size_t>(packed_bytes) : static_cast<size_t>(n) * isz;
     int rc = ensure_staging(g, bytes);
     if (rc != GSH_OK) return rc;
     const int slot = g->slot;
@@ -317,7 +326,8 @@ int push_common(gsh_stream_group* g, const void* items, bool items_on_device, ui
     for (size_t i = 0; i < g->rings.size(); i++)
         {
             GSH_HIP(hipSetDevice(g->rings[i]->device));
-            rc = gsh::stream_write_device_items(g->rings[i], g->stage[slot][i], n, item_type, inverted_spectrum ? 1 : 0, g->rings[i]->stream);
+            rc = fmt != nullptr ? gsh::stream_write_device_packed(g->rings[i], g->stage[slot][i], packed, n, inverted_spectrum ? 1 : 0, g->rings[i]->stream)
+                                : gsh::stream_write_device_items(g->rings[i], g->stage[slot][i], n, item_type, inverted_spectrum ? 1 : 0, g->rings[i]->stream);
             if (rc != GSH_OK) return rc;
         }
     return GSH_OK;
@@ -458,6 +468,18 @@ extern "C"
     int gsh_stream_group_push_device(gsh_stream_group_t* g, const void* device_items, uint64_t n, int item_type, int inverted_spectrum, uint64_t* first_index)
     {
         return push_common(g, device_items, true, n, item_type, inverted_spectrum, first_index);
+    }
+
+    int gsh_stream_group_push_packed(gsh_stream_group_t* g, const gsh_packed_format* fmt, const void* host_bytes, uint64_t n_samples, int inverted_spectrum,
+        uint64_t* first_index)
+    {
+        return push_common(g, host_bytes, false, n_samples, GSH_ITEM_BYTE, inverted_spectrum, first_index, fmt);
+    }
+
+    int gsh_stream_group_push_packed_device(gsh_stream_group_t* g, const gsh_packed_format* fmt, const void* device_bytes, uint64_t n_samples,
+        int inverted_spectrum, uint64_t* first_index)
+    {
+        return push_common(g, device_bytes, true, n_samples, GSH_ITEM_BYTE, inverted_spectrum, first_index, fmt);
     }
 
     int gsh_stream_group_rccl_info(const gsh_stream_group_t* g, int32_t* rccl_ranks, int32_t* rccl_version, uint64_t* collectives)

@@ -402,6 +402,26 @@ uint64_t Hip_Sample_Ring::push_ibyte(const int8_t* iq, uint64_t n, bool inverted
 }
 
 
+uint64_t Hip_Sample_Ring::push_packed(const gsh_packed_format& fmt, const void* bytes, uint64_t n_samples, bool inverted_spectrum)
+{
+    if (d_handle == nullptr) return UINT64_MAX;
+    uint64_t first = 0;
+    {
+        std::lock_guard<std::mutex> lk(d_mutex);
+        const int rc = d_group == nullptr ? gsh_stream_push_packed(d_handle, &fmt, bytes, n_samples, inverted_spectrum ? 1 : 0, &first)
+                                          : gsh_stream_group_push_packed(d_group, &fmt, bytes, n_samples, inverted_spectrum ? 1 : 0, &first);
+        if (rc != GSH_OK || (d_group != nullptr && gsh_stream_group_wait(d_group) != GSH_OK))  // (`bytes` is the caller's again on return)
+            {
+                set_error(gsh_last_error());
+                return UINT64_MAX;
+            }
+        d_next.store(first + n_samples, std::memory_order_release);
+    }
+    d_pushed.notify_all();
+    return first;
+}
+
+
 void Hip_Sample_Ring::range(uint64_t* oldest, uint64_t* next) const
 {
     std::lock_guard<std::mutex> lk(d_mutex);

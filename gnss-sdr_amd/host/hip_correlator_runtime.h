@@ -61,6 +61,9 @@ public:
     uint64_t push(const std::complex<float>* samples, uint64_t n, bool inverted_spectrum = false);
     uint64_t push_ishort(const int16_t* iq, uint64_t n, bool inverted_spectrum = false);  //!< item_type ishort / cshort
     uint64_t push_ibyte(const int8_t* iq, uint64_t n, bool inverted_spectrum = false);    //!< item_type ibyte / cbyte
+    /*! packed 2-bit / 4-bit complex front-end samples (Two_Bit_Packed iq / qi, Two_Bit_Cpx, Four_Bit_Cpx): the packed bytes cross PCIe (and RCCL), the
+        engine unpacks them into the ring(s).  n_samples: a whole number of the format's input items. */
+    uint64_t push_packed(const gsh_packed_format& fmt, const void* bytes, uint64_t n_samples, bool inverted_spectrum = false);
     /*! What a block that shares the ring with other channel threads calls with the samples of ITS input buffer, named by their absolute index:
         range check, de-duplication and append happen under ONE acquisition of the ring's lock, so two threads that see the same `next` cannot
         both append.  Samples already resident are skipped (another channel of the stream pushed them); the rest is appended through page-locked

@@ -12,6 +12,101 @@ ITEM_TYPES = {"gr_complex": GSH_ITEM_GR_COMPLEX, "ishort": GSH_ITEM_SHORT, "csho
 _NP = {GSH_ITEM_GR_COMPLEX: np.complex64, GSH_ITEM_SHORT: np.int16, GSH_ITEM_BYTE: np.int8}
 
 
+def _flag(v) -> int:
+    """a boolean property as the reference's configuration reads it (true / false, or a Python bool)"""
+    if isinstance(v, str):
+        if v.strip().lower() not in ("true", "false", "1", "0"):
+            raise ValueError(f"not a boolean: {v!r}")
+        return int(v.strip().lower() in ("true", "1"))
+    return int(bool(v))
+
+
+class PackedFormat:
+    """gsh_packed_format: packed 2-bit / 4-bit front-end samples, unpacked on the device the way the reference's signal source unpacks them
+    (include/gnss_sdr_hip.h).  Build it from the source's configuration with from_signal_source()."""
+    TWO_BIT, TWO_BIT_CPX, FOUR_BIT_CPX, NSR, NTLAB = 1, 2, 3, 4, 5
+    REAL, IQ, QI = 0, 1, 2
+    IMPLEMENTATIONS = {"Two_Bit_Packed_File_Signal_Source": TWO_BIT, "Two_Bit_Cpx_File_Signal_Source": TWO_BIT_CPX,
+                       "Four_Bit_Cpx_File_Signal_Source": FOUR_BIT_CPX, "Nsr_File_Signal_Source": NSR, "NTLab_File_Signal_Source": NTLAB}
+    SAMPLE_TYPES = {"real": REAL, "iq": IQ, "qi": QI}
+
+    def __init__(self, family: int, sample_type: int = REAL, item_size: int = 1, big_endian_bytes: bool = False, big_endian_items: bool = False,
+                 rf_channels: int = 0, channel: int = 0):
+        self.family, self.sample_type, self.item_size = int(family), int(sample_type), int(item_size)
+        self.big_endian_bytes, self.big_endian_items = int(big_endian_bytes), int(big_endian_items)
+        self.rf_channels, self.channel = int(rf_channels), int(channel)
+
+    @classmethod
+    def from_signal_source(cls, implementation: str, **properties) -> "PackedFormat":
+        """The format of SignalSource.implementation = `implementation` with the reference's property names and defaults
+        (two_bit_packed_file_signal_source.cc:38-41: item_type byte, sample_type real, big_endian_items true, big_endian_bytes false;
+        four_bit_cpx_file_signal_source.cc:38: sample_type iq; ntlab_file_signal_source.cc:41-42: RF_channels 4).  `channel` (not a reference
+        property) picks the RF channel of an NTLab stream for unpack_device / a packed FirFilter.  Other properties of the source are ignored."""
+        if implementation not in cls.IMPLEMENTATIONS:
+            raise ValueError(f"{implementation!r} is not a packed signal source ({', '.join(cls.IMPLEMENTATIONS)})")
+        fam = cls.IMPLEMENTATIONS[implementation]
+        item_type = properties.get("item_type", "byte")
+        if item_type not in (("byte", "short") if fam == cls.TWO_BIT else ("byte",)):
+            raise ValueError(f"item_type {item_type!r} is not supported by {implementation}")
+        if fam == cls.TWO_BIT:
+            st = properties.get("sample_type", "real")
+            return cls(fam, cls.SAMPLE_TYPES[st], 2 if item_type == "short" else 1, _flag(properties.get("big_endian_bytes", False)),
+                       _flag(properties.get("big_endian_items", True)))
+        if fam == cls.FOUR_BIT_CPX:
+            st = properties.get("sample_type", "iq")
+            if st not in ("iq", "qi"):
+                raise ValueError(f"sample_type {st!r} is not iq / qi")
+            return cls(fam, cls.SAMPLE_TYPES[st])
+        if fam == cls.NTLAB:
+            return cls(fam, cls.REAL, rf_channels=int(properties.get("RF_channels", 4)), channel=int(properties.get("channel", 0)))
+        return cls(fam, cls.IQ if fam == cls.TWO_BIT_CPX else cls.REAL)
+
+    def with_channel(self, channel: int) -> "PackedFormat":
+        return PackedFormat(self.family, self.sample_type, self.item_size, self.big_endian_bytes, self.big_endian_items, self.rf_channels, channel)
+
+    @property
+    def is_complex(self) -> bool:
+        return self.family in (self.TWO_BIT_CPX, self.FOUR_BIT_CPX) or (self.family == self.TWO_BIT and self.sample_type != self.REAL)
+
+    @property
+    def samples_per_byte(self) -> int:
+        """samples of one RF channel per packed byte"""
+        if self.family == self.TWO_BIT:
+            return 2 if self.is_complex else 4
+        return {self.TWO_BIT_CPX: 2, self.FOUR_BIT_CPX: 1, self.NSR: 4, self.NTLAB: 1}[self.family]
+
+    def struct(self) -> "_lib.PackedFormat":
+        return _lib.PackedFormat(self.family, self.sample_type, self.item_size, self.big_endian_bytes, self.big_endian_items, self.rf_channels,
+                                 self.channel, 0)
+
+    def __repr__(self):
+        return (f"PackedFormat(family={self.family}, sample_type={self.sample_type}, item_size={self.item_size}, big_endian_bytes={self.big_endian_bytes}, "
+                f"big_endian_items={self.big_endian_items}, rf_channels={self.rf_channels}, channel={self.channel})")
+
+
+def packed_bytes(fmt: PackedFormat, n_samples: int) -> int:
+    """gsh_packed_bytes: bytes that hold n_samples samples per RF channel (GshError for a bad format or a partial input item).  No GPU."""
+    out = C.c_uint64(0)
+    f = fmt.struct()
+    check(_lib.load().gsh_packed_bytes(C.byref(f), int(n_samples), C.byref(out)))
+    return int(out.value)
+
+
+def unpack_device(device: int, fmt: PackedFormat, src_ptr: int, first_sample: int, n_samples: int, dst_ptr: int, inverted_spectrum: bool = False,
+                  hip_stream: int = 0) -> None:
+    """gsh_unpack_device: complex64 (complex families) or float32 of fmt.channel (real families) for samples [first_sample, first_sample + n) of a
+    device-resident packed buffer."""
+    f = fmt.struct()
+    check(_lib.load().gsh_unpack_device(device, C.byref(f), C.c_void_p(src_ptr), int(first_sample), int(n_samples), int(inverted_spectrum),
+                                        C.c_void_p(dst_ptr), C.c_void_p(hip_stream) if hip_stream else None))
+
+
+def _packed_host(fmt: PackedFormat, data, n_samples):
+    a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data).view(np.uint8).reshape(-1)
+    n = a.size * fmt.samples_per_byte if n_samples is None else int(n_samples)
+    return a, n
+
+
 class SampleStream:
     def __init__(self, capacity_samples: int, max_window_samples: int, device: int = 0):
         self._lib = _lib.load()
@@ -80,6 +175,39 @@ class SampleStream:
             check(self._lib.gsh_host_unregister(C.c_void_p(lo)))
         return int(first.value)
 
+    def push_packed(self, fmt: PackedFormat, data, inverted_spectrum: bool = False, n_samples: int | None = None) -> int:
+        """gsh_stream_push_packed: packed complex samples held in host memory (every sample of `data` unless n_samples says fewer); synchronous."""
+        a, n = _packed_host(fmt, data, n_samples)
+        f, first = fmt.struct(), C.c_uint64(0)
+        check(self._lib.gsh_stream_push_packed(self._h, C.byref(f), C.c_void_p(a.ctypes.data) if a.size else None, n, int(inverted_spectrum), C.byref(first)))
+        return int(first.value)
+
+    def push_packed_device(self, fmt: PackedFormat, device_ptr: int, n_samples: int, inverted_spectrum: bool = False, hip_stream: int = 0) -> int:
+        f, first = fmt.struct(), C.c_uint64(0)
+        check(self._lib.gsh_stream_push_packed_device(self._h, C.byref(f), C.c_void_p(device_ptr), int(n_samples), int(inverted_spectrum),
+                                                      C.c_void_p(hip_stream) if hip_stream else None, C.byref(first)))
+        return int(first.value)
+
+    def push_packed_pinned_async(self, fmt: PackedFormat, data: np.ndarray, inverted_spectrum: bool = False, n_samples: int | None = None) -> int:
+        """gsh_stream_push_packed_pinned_async: `data` lies in page-locked memory (gsh_host_register) and must stay untouched until wait_copied() /
+        wait_copied_upto() covers the push; the DMA and the unpack are queued, nothing waits."""
+        a, n = _packed_host(fmt, data, n_samples)
+        self._keep_async = getattr(self, "_keep_async", [])[-3:] + [a]
+        f, first = fmt.struct(), C.c_uint64(0)
+        check(self._lib.gsh_stream_push_packed_pinned_async(self._h, C.byref(f), C.c_void_p(a.ctypes.data) if a.size else None, n, int(inverted_spectrum),
+                                                            C.byref(first)))
+        return int(first.value)
+
+    def wait_copied(self) -> None:
+        check(self._lib.gsh_stream_wait_copied(self._h))
+
+    def wait_copied_upto(self, end_index: int) -> int:
+        """blocks until every push that covers samples below end_index has been read out of the caller's memory; returns the index up to which the
+        ring is known to be complete"""
+        upto = C.c_uint64(0)
+        check(self._lib.gsh_stream_wait_copied_upto(self._h, int(end_index), C.byref(upto)))
+        return int(upto.value)
+
     def wait(self) -> None:
         check(self._lib.gsh_stream_wait(self._h))
 
@@ -115,12 +243,18 @@ class FirFilter:
     """gsh_fir_*: frequency-translating decimating FIR filter with stream history (freq_xlating_fir_filter_ccf / fir_filter_ccf on the device)."""
     KINDS = {"gr_complex": 0, "float": 1, "short": 2, "byte": 3}
 
-    def __init__(self, taps, decimation: int = 1, center_freq_hz: float = 0.0, sampling_freq_hz: float = 1.0, input_kind: str = "gr_complex", device: int = 0):
+    def __init__(self, taps, decimation: int = 1, center_freq_hz: float = 0.0, sampling_freq_hz: float = 1.0, input_kind="gr_complex", device: int = 0):
+        """input_kind: "gr_complex", "float", "short", "byte", or a PackedFormat (gsh_fir_create_packed: process_device then reads packed bytes, n_in
+        counting samples of the format's RF channel)."""
         self._lib = _lib.load()
         self._h = C.c_void_p()
         t = np.ascontiguousarray(taps, np.float32)
         self.decimation = decimation
-        check(self._lib.gsh_fir_create(device, fptr(t), len(t), decimation, center_freq_hz, sampling_freq_hz, self.KINDS[input_kind], C.byref(self._h)))
+        if isinstance(input_kind, PackedFormat):
+            f = input_kind.struct()
+            check(self._lib.gsh_fir_create_packed(device, fptr(t), len(t), decimation, center_freq_hz, sampling_freq_hz, C.byref(f), C.byref(self._h)))
+        else:
+            check(self._lib.gsh_fir_create(device, fptr(t), len(t), decimation, center_freq_hz, sampling_freq_hz, self.KINDS[input_kind], C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -347,6 +481,23 @@ class StreamGroup:
         first = C.c_uint64(0)
         ptr = C.c_void_p(items.ctypes.data) if items is not None else None
         check(self._lib.gsh_stream_group_push(self._h, ptr, n, ITEM_TYPES[item_type], int(inverted_spectrum), C.byref(first)))
+        return int(first.value)
+
+    def push_packed(self, fmt: PackedFormat, data, n_samples: int | None = None, inverted_spectrum: bool = False) -> int:
+        """gsh_stream_group_push_packed: every rank calls it; rank 0's process supplies the packed bytes, the others pass data = None and n_samples"""
+        f, first = fmt.struct(), C.c_uint64(0)
+        if data is None:
+            ptr, n = None, int(n_samples)
+        else:
+            a, n = _packed_host(fmt, data, n_samples)
+            ptr = C.c_void_p(a.ctypes.data) if a.size else None
+        check(self._lib.gsh_stream_group_push_packed(self._h, C.byref(f), ptr, n, int(inverted_spectrum), C.byref(first)))
+        return int(first.value)
+
+    def push_packed_device(self, fmt: PackedFormat, device_ptr: int | None, n_samples: int, inverted_spectrum: bool = False) -> int:
+        f, first = fmt.struct(), C.c_uint64(0)
+        check(self._lib.gsh_stream_group_push_packed_device(self._h, C.byref(f), C.c_void_p(device_ptr) if device_ptr else None, int(n_samples),
+                                                            int(inverted_spectrum), C.byref(first)))
         return int(first.value)
 
     def wait(self) -> None:

@@ -333,6 +333,65 @@ extern "C"
     /* stand-alone conversion of n device-resident items to complex64 (device_dst 8-byte aligned), asynchronous on hip_stream */
     int gsh_convert_samples_device(int device, const void* device_items, int item_type, int inverted_spectrum, void* device_dst, uint64_t n,
         void* hip_stream);
+    /* ---- packed 2-bit / 4-bit front-end samples, unpacked on the device with the arithmetic of the reference's unpack blocks
+     * (src/algorithms/signal_source/gnuradio_blocks/unpack_*.cc) followed by the GNU Radio conversion the signal source puts behind them.
+     * Paths below: adapters/ = src/algorithms/signal_source/adapters/, blocks/ = src/algorithms/signal_source/gnuradio_blocks/.
+     *   GSH_PACKED_TWO_BIT       Two_Bit_Packed_File_Signal_Source (adapters/two_bit_packed_file_signal_source.cc:38-145): blocks/unpack_2bit_samples.cc
+     *                            (2s + 1 of each signed 2-bit field), then char_to_float (real) or interleaved_char_to_complex (iq / qi).
+     *   GSH_PACKED_TWO_BIT_CPX   Two_Bit_Cpx_File_Signal_Source (adapters/two_bit_cpx_file_signal_source.cc:72-81): blocks/unpack_byte_2bit_cpx_samples.cc,
+     *                            then interleaved_short_to_complex(false, true).  Complex, 2 samples per byte.
+     *   GSH_PACKED_FOUR_BIT_CPX  Four_Bit_Cpx_File_Signal_Source (adapters/four_bit_cpx_file_signal_source.cc:38-55,118-121): blocks/unpack_byte_4bit_samples.cc,
+     *                            then interleaved_short_to_complex(false, qi).  Complex, 1 sample per byte.
+     *   GSH_PACKED_NSR           Nsr_File_Signal_Source (adapters/nsr_file_signal_source.cc:69-76): blocks/unpack_byte_2bit_samples.cc, real float -2..1,
+     *                            4 samples per byte.
+     *   GSH_PACKED_NTLAB         NTLab_File_Signal_Source (adapters/ntlab_file_signal_source.cc:41-45,88,100-127): blocks/unpack_ntlab_2bit_samples.cc,
+     *                            sign / magnitude +-1 / +-3, one real stream per RF channel; RF_channels = 4 only (1 and 2 are refused: the
+     *                            reference block reads past its input there, blocks/unpack_ntlab_2bit_samples.cc:38,57-77).
+     * The real families (TWO_BIT with sample_type real, NSR, NTLAB) are IF samples: they enter a ring through a packed FIR (gsh_fir_create_packed)
+     * and gsh_stream_push_device, never directly.  Sample counts are samples of ONE RF channel and must be whole input items (the reference blocks
+     * are sync_interpolators: they consume whole items).  Zero-initialise the descriptor and set what applies. */
+#define GSH_PACKED_TWO_BIT 1
+#define GSH_PACKED_TWO_BIT_CPX 2
+#define GSH_PACKED_FOUR_BIT_CPX 3
+#define GSH_PACKED_NSR 4
+#define GSH_PACKED_NTLAB 5
+#define GSH_PACKED_REAL 0 /* sample_type "real" */
+#define GSH_PACKED_IQ 1   /* sample_type "iq" */
+#define GSH_PACKED_QI 2   /* sample_type "qi" */
+    typedef struct
+    {
+        int32_t family;           /* GSH_PACKED_TWO_BIT .. GSH_PACKED_NTLAB (the SignalSource.implementation) */
+        int32_t sample_type;      /* TWO_BIT: "sample_type", default real (two_bit_packed_file_signal_source.cc:39); FOUR_BIT_CPX: iq / qi, default iq
+                                   * (four_bit_cpx_file_signal_source.cc:38); REAL for NSR and NTLAB; IQ for TWO_BIT_CPX */
+        int32_t item_size;        /* TWO_BIT: 1 ("item_type" byte, the default of FileSourceBase) or 2 (short); every other family: 1 */
+        int32_t big_endian_bytes; /* TWO_BIT: "big_endian_bytes", default false (two_bit_packed_file_signal_source.cc:41): sample order within a byte reversed */
+        int32_t big_endian_items; /* TWO_BIT: "big_endian_items", default true (:40): with item_size 2 the two bytes of an item swap first; little-endian
+                                   * short items are read as bytes (:63-77) */
+        int32_t rf_channels;      /* NTLAB: "RF_channels", default 4 (ntlab_file_signal_source.cc:41-42), 4 only; every other family: 0 or 1 */
+        int32_t channel;          /* NTLAB: the RF channel unpacked by gsh_unpack_device / the packed FIR (0..3); every other family: 0 */
+        int32_t reserved;         /* 0 */
+    } gsh_packed_format;
+    /* packed bytes that hold n_samples samples per RF channel; GSH_ERR_INVALID for a bad descriptor or a count that is not whole items.  No GPU. */
+    int gsh_packed_bytes(const gsh_packed_format* fmt, uint64_t n_samples, uint64_t* bytes);
+    /* samples [first_sample, first_sample + n_samples) of the packed buffer d_src (sample 0 = the first of its first byte) -> d_dst: complex64 for
+     * the complex families (conjugated when inverted_spectrum), float32 of fmt->channel for the real ones (inverted_spectrum must be 0).
+     * first_sample may fall inside a byte; d_dst 8-byte aligned (complex) or 4-byte aligned (real).  Asynchronous on hip_stream. */
+    int gsh_unpack_device(int device, const gsh_packed_format* fmt, const void* d_src, uint64_t first_sample, uint64_t n_samples, int inverted_spectrum,
+        void* d_dst, void* hip_stream);
+    /* the push entry points above for packed complex samples: the packed bytes cross PCIe, the unpack writes complex64 straight into the ring.
+     * Same rules as gsh_stream_push / _device / _pinned_async (gsh_stream_wait_copied and _upto cover the _pinned_async form).  A real family is
+     * refused (GSH_ERR_INVALID): IF samples go through gsh_fir_create_packed. */
+    int gsh_stream_push_packed(gsh_stream_t* s, const gsh_packed_format* fmt, const void* bytes, uint64_t n_samples, int inverted_spectrum, uint64_t* first_index);
+    int gsh_stream_push_packed_device(gsh_stream_t* s, const gsh_packed_format* fmt, const void* device_bytes, uint64_t n_samples, int inverted_spectrum,
+        void* hip_stream, uint64_t* first_index);
+    int gsh_stream_push_packed_pinned_async(gsh_stream_t* s, const gsh_packed_format* fmt, const void* bytes, uint64_t n_samples, int inverted_spectrum,
+        uint64_t* first_index);
+    /* gsh_stream_group_push / _device for packed complex samples: rank 0 stages the packed bytes, the group replicates exactly those (padded as
+     * gsh_stream_group_plan pads them), every rank unpacks into its own ring */
+    int gsh_stream_group_push_packed(gsh_stream_group_t* g, const gsh_packed_format* fmt, const void* host_bytes, uint64_t n_samples, int inverted_spectrum,
+        uint64_t* first_index);
+    int gsh_stream_group_push_packed_device(gsh_stream_group_t* g, const gsh_packed_format* fmt, const void* device_bytes, uint64_t n_samples,
+        int inverted_spectrum, uint64_t* first_index);
     /* Direct (nearest-neighbour) resampler, the arithmetic of direct_resampler_conditioner_cc (src/algorithms/resampler/gnuradio_blocks/
      * direct_resampler_conditioner_cc.cc:39-129; used by the signal conditioner and the acquisition decimator, gnss_flowgraph.cc:1165-1209):
      * 32-bit phase accumulator, a sample is copied on every wrap.  Stateless form: outputs are numbered from the start of the stream,
@@ -353,6 +412,11 @@ extern "C"
         gsh_fir_t** out);
     void gsh_fir_destroy(gsh_fir_t* f);
     int gsh_fir_process_device(gsh_fir_t* f, const void* device_in, uint64_t n_in, void* device_out, uint64_t max_out, uint64_t* n_out, void* hip_stream);
+    /* the same filter fed packed front-end bytes (gsh_packed_format): gsh_fir_process_device's device_in is the packed block and n_in counts
+     * samples of fmt->channel, a whole number of input items per call.  Output and history are those of gsh_fir_create fed the unpacked samples
+     * (real families: input_kind 1 with the floats of gsh_unpack_device; complex families: input_kind 0, not conjugated). */
+    int gsh_fir_create_packed(int device, const float* taps, int n_taps, int decimation, double center_freq_hz, double sampling_freq_hz,
+        const gsh_packed_format* fmt, gsh_fir_t** out);
     /* bind a bank to a ring: from now on gsh_corr_job.sample_offset is an ABSOLUTE sample index; a job whose window is not
      * fully resident (or longer than max_window_samples) fails with GSH_ERR_INVALID.  NULL detaches.
      * Residency is checked when the job table is staged (gsh_bank_correlate / gsh_bank_upload_jobs): a table uploaded once and
