@@ -25,6 +25,11 @@ namespace GSH_MC_NS
 constexpr int MC_THREADS = GSH_MC_THREADS;
 constexpr int MC_WAVES = MC_THREADS / 64;
 constexpr int MC_MARGIN = 32;  // guard entries on each side of the LDS code table
+// HALF-CHIP TAPS (round 7, packed_trip): the flavour for E/P/L at exactly -0.5 / 0 / +0.5 chip keeps a DOUBLED copy of the guard-banded table, D[2 i] = D[2 i + 1] =
+// table[i], at LDS address 0 and the plain table behind it at a constant word offset (the per-tap and edge trips read that one, with the offset in their immediates).
+// The doubled region is sized for the longest code the flavour takes, so that the plain table's place does not depend on the job.
+constexpr int MC_HALF_MAX_CODE_LEN = 1024;                               // the half-index h = floor(2 w) comes out of a half-precision pattern: h < 2048
+constexpr int MC_HALF_WORDS = 2 * (MC_HALF_MAX_CODE_LEN + 2 * MC_MARGIN);  // 2 176 words = 8 704 bytes
 #ifndef GSH_MC_SCAN_ALL_AT_ONCE
 #define GSH_MC_SCAN_ALL_AT_ONCE 1  // wave sums of the 1 024-thread kernel: one v_add_f32_dpp per value and step (round 4: 7.63 -> 7.50 us per period)
 #endif
@@ -528,12 +533,14 @@ __device__ __forceinline__ v2f pk_add_shi(v2f v, v2f k)
 //     the per-tap chains for that trip as before.
 // The products and their order of summation are the same either way: the outputs are bit-identical with the switch off
 // (tests/test_tracking_gpu.py::test_paired_taps_are_bit_identical).
-template <int NT, bool ZP, bool AUX, int NCH, bool PA = false, bool PB = false, bool KC = false>
+template <int NT, bool ZP, bool AUX, int NCH, bool PA = false, bool PB = false, bool KC = false, bool HALF = false>
 __device__ __forceinline__ void packed_trip(const JobCtx& c, const float* __restrict__ tab, const v2f (&shp)[NT],
     v2f k_step_nrem, v2f aux_shp, bool aux_on, v2f nfA, v2f nfB, v2f yA0, v2f yA1, v2f yB0, v2f yB1, v2f (&A0)[NT], v2f (&A1)[NT], v2f (&B0)[NT],
     v2f (&B1)[NT], v2f& XA0, v2f& XA1, v2f& XB0, v2f& XB1, v2f scaled_step_nrem = (v2f){0.0f, 0.0f}, v2f scaled_shP_shL = (v2f){0.0f, 0.0f})
 {
     static_assert(!(PA || PB) || NT == 3, "paired taps: early / prompt / late");
+    static_assert(!HALF || (GSH_MC_PKRTZ && KC && ZP && !AUX && NCH == 2 && NT == 3), "half-chip taps: E/P/L, zero-shift prompt, whole-code table, two chunks per trip");
+    constexpr int TB = HALF ? MC_HALF_WORDS : 0;  // word offset of the plain table (KC: a constant; the doubled table of the half-chip flavour lies in front of it)
     const v2f zero = {0.0f, 0.0f};
     v2f aB = zero;
     if (NCH == 2) aB = pk_mul_slo(nfB, k_step_nrem);
@@ -552,7 +559,7 @@ __device__ __forceinline__ void packed_trip(const JobCtx& c, const float* __rest
             {
                 unsigned byte_addr;
                 asm("v_lshlrev_b32 %0, 2, %1" : "=v"(byte_addr) : "v"(k));
-                return reinterpret_cast<lds_float_ptr>(byte_addr)[MC_MARGIN + D];  // KC: `tab` IS LDS address 0 (the caller checks)
+                return reinterpret_cast<lds_float_ptr>(byte_addr)[TB + MC_MARGIN + D];  // KC: `tab` IS LDS word TB (the caller checks)
             }
         else
             return tab[k + off + D];
@@ -636,6 +643,57 @@ __device__ __forceinline__ void packed_trip(const JobCtx& c, const float* __rest
                 pk_fma_hi(S1[2], y1, d.el1);
             };
 #if GSH_MC_PKRTZ
+            if constexpr (HALF)
+                {
+                    // ALL THREE TAPS FROM ONE CHAIN (round 7).  With the taps exactly half a chip apart the prompt chain w = fl(fl(step n) - rem) determines all three chips:
+                    // inside one binade (the caller's judgement of the wave's 128 samples, early tap's low end to late tap's high end, before and after the subtraction)
+                    // adding -+0.5 commutes with both roundings -- 0.5 is an even multiple of the quantum -- so with h = floor(2 w) (2 w is exact)
+                    //     k_P = h >> 1,   k_L = (h + 1) >> 1,   k_E = (h - 1) >> 1
+                    // and in the doubled table D[h] = code[h >> 1] the three code values are the consecutive words D[h - 1], D[h], D[h + 1].  The chain runs on constants
+                    // scaled by 2^-23 (the caller's), so the half-precision pattern of v_cvt_pkrtz_f16_f32 IS floor(2 w) for 2 w < 2048: per chunk one multiply, one add,
+                    // one conversion and two address shifts instead of two chains.  Same products into the same accumulators as the forms below.
+                    const v2f uA = pk_add_shi(pk_mul_slo(nfA, scaled_step_nrem), scaled_step_nrem);
+                    const v2f uB = pk_add_shi(pk_mul_slo(nfB, scaled_step_nrem), scaled_step_nrem);
+                    auto two_halves = [](v2f u, unsigned& byte0, unsigned& byte1) {
+                        unsigned pk;
+                        asm("v_cvt_pkrtz_f16_f32 %0, %1, %2" : "=v"(pk) : "v"(u.x), "v"(u.y));
+                        asm("v_lshlrev_b16_e32 %0, 2, %1" : "=v"(byte0) : "v"(pk));  // (h < 2040: 4 h fits the 16 bits)
+                        asm("v_lshrrev_b32_e32 %0, 14, %1" : "=v"(byte1) : "v"(pk));
+                    };
+                    auto at = [&](unsigned byte_addr, auto dc) -> float {
+                        constexpr int D = decltype(dc)::value;
+                        return reinterpret_cast<lds_float_ptr>(byte_addr)[2 * MC_MARGIN + D];  // the doubled table IS LDS address 0
+                    };
+                    using dp1 = std::integral_constant<int, 1>;
+                    unsigned b0, b1, b2, b3;
+                    two_halves(uA, b0, b1);
+                    two_halves(uB, b2, b3);
+                    v2f epA0, epA1, lA, epB0, epB1, lB;  // (early, prompt) of each sample: one 64-bit pair per look-up; the late values of a pair of samples together
+                    epA0.x = at(b0, dm1{});
+                    epA0.y = at(b0, d0{});
+                    epA1.x = at(b1, dm1{});
+                    epA1.y = at(b1, d0{});
+                    lA.x = at(b0, dp1{});
+                    lA.y = at(b1, dp1{});
+                    epB0.x = at(b2, dm1{});
+                    epB0.y = at(b2, d0{});
+                    epB1.x = at(b3, dm1{});
+                    epB1.y = at(b3, d0{});
+                    lB.x = at(b2, dp1{});
+                    lB.y = at(b3, dp1{});
+                    __builtin_amdgcn_sched_barrier(0);
+                    auto accumulate_half = [&](v2f ep0, v2f ep1, v2f l, v2f y0, v2f y1, v2f (&S0)[NT], v2f (&S1)[NT]) {
+                        pk_fma_lo(S0[0], y0, ep0);
+                        pk_fma_lo(S1[0], y1, ep1);
+                        pk_fma_hi(S0[1], y0, ep0);
+                        pk_fma_hi(S1[1], y1, ep1);
+                        pk_fma_lo(S0[2], y0, l);
+                        pk_fma_hi(S1[2], y1, l);
+                    };
+                    accumulate_half(epA0, epA1, lA, yA0, yA1, A0, A1);
+                    accumulate_half(epB0, epB1, lB, yB0, yB1, B0, B1);
+                    return;
+                }
             Codes dA, dB;
             if constexpr (KC)
                 {
@@ -820,11 +878,13 @@ __device__ __forceinline__ void paired_accumulate(const PairedCodes& d, v2f y0, 
 // second, pa w / pa w inc for chunk B: three more complex products per trip (six packed instructions) -- and all four products of a tap go into the same
 // accumulator; the fold at the end is gone.  24 accumulator registers become 6, which is what lets a 1 024-thread work-group (128 VGPRs) run TWO chunks per
 // trip: the per-trip overhead (phasor step, index step, loop control, edge tests, the wait for the look-ups) is paid once per four samples instead of once per two.
-template <int NT, bool ZP, bool AUX, int NCH, int PF, bool DER = false, bool KC = false, bool MRG = false>
+// HALF (round 7): the paired trips take all three taps from the prompt chain and the doubled table (packed_trip); the caller vouches for shifts of exactly -0.5 / 0 / +0.5
+template <int NT, bool ZP, bool AUX, int NCH, int PF, bool DER = false, bool KC = false, bool MRG = false, bool HALF = false>
 __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2* __restrict__ base, const float* __restrict__ tab,
     const float (&sh)[NT], float2 (&acc)[NT], float2* acc_aux)
 {
     static_assert(NCH == 1 || NCH == 2, "one or two chunks per trip");
+    static_assert(!HALF || (DER && KC && !MRG), "half-chip taps: a paired-tap flavour of the whole-code table");
     constexpr int PPC = MC_PAIRS_PER_CHUNK;
     constexpr int RESEED = packed_reseed_trips(NCH);     // trips between exact re-seeds
     constexpr int TBL = 60;                               // re-seed entries per table fill
@@ -943,7 +1003,8 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
 #if GSH_MC_PKRTZ
     // the chain constants times 2^-24 for the paired trips' two-floors-per-instruction form (packed_trip); exact unless one of them is so small that its scaled value
     // would be denormal -- then no trip of this segment takes the paired form (scaled_ok, below)
-    constexpr float PK_SCALE = 0x1p-24f;
+    // (half-chip taps: 2^-23 -- the pattern is then floor(2 w), the index into the doubled table)
+    constexpr float PK_SCALE = HALF ? 0x1p-23f : 0x1p-24f;
     auto scales_exactly = [](float x) -> bool { return x == 0.0f || fabsf(x) >= 0x1p-100f; };
     auto uniform = [](float x) -> float { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); };  // (a product is a VGPR value)
     const v2f scaled_step_nrem = {uniform(c.code_step * PK_SCALE), uniform(-c.rem_code * PK_SCALE)};
@@ -1083,7 +1144,9 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
                 // (only the form that converts two chains per instruction needs the tighter bound and the scaled constants: whole-code tables, two chunks per trip --
                 //  packed_trip.  The windowed tables of long codes pair their taps up to 2^16 as before.)
                 constexpr bool TWO_FLOORS = GSH_MC_PKRTZ && KC && NCH == 2 && NT == 3;
-                constexpr float HI = TWO_FLOORS ? 2040.0f : 65536.0f;  // the half-precision pattern of u * 2^-24 is floor(u) below 2048
+                // the half-precision pattern of u * 2^-24 is floor(u) below 2048; half-chip taps: that of w * 2^-23 is floor(2 w) for 2 w below 2048 (the range judged
+                // runs from the early chain's low end to the late chain's high end, so it holds the prompt chain w)
+                constexpr float HI = HALF ? 1020.0f : (TWO_FLOORS ? 2040.0f : 65536.0f);
                 const bool one_binade_a = (lo1 >= 1.0f) && (hi1 < HI) && ((__float_as_uint(lo1) >> 23) == (__float_as_uint(hi1) >> 23));
                 const bool one_binade_u = (lo2 >= 1.0f) && (hi2 < HI) && ((__float_as_uint(lo2) >> 23) == (__float_as_uint(hi2) >> 23));
 #if GSH_MC_PKRTZ
@@ -1144,7 +1207,7 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
 #ifndef GSH_MC_EARLY_CODES
 #define GSH_MC_EARLY_CODES 0
 #endif
-        constexpr bool EARLY_CODES = GSH_MC_EARLY_CODES && FA && FB && NCH == 2 && NT == 3 && !AUX && !MRG;
+        constexpr bool EARLY_CODES = GSH_MC_EARLY_CODES && FA && FB && NCH == 2 && NT == 3 && !AUX && !MRG && !HALF;
         PairedCodes dA, dB;
         if constexpr (EARLY_CODES)
             {
@@ -1199,8 +1262,8 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
         else if constexpr (MRG)  // (one set: the four references name the same registers, the accumulates follow one another)
             packed_trip<NT, ZP, AUX, NCH, FA, FB, KC>(c, tab, shp, k_step_nrem, aux_shp, aux_on, ia, ib, yA0, yA1, yB0, yB1, A0, A0, A0, A0, XA0, XA0, XA0, XA0);
         else
-            packed_trip<NT, ZP, AUX, NCH, FA, FB, KC>(c, tab, shp, k_step_nrem, aux_shp, aux_on, ia, ib, yA0, yA1, yB0, yB1, A0, A1, B0, B1, XA0, XA1, XB0, XB1, scaled_step_nrem,
-                scaled_shP_shL);
+            packed_trip<NT, ZP, AUX, NCH, FA, FB, KC, HALF>(c, tab, shp, k_step_nrem, aux_shp, aux_on, ia, ib, yA0, yA1, yB0, yB1, A0, A1, B0, B1, XA0, XA1, XB0, XB1,
+                scaled_step_nrem, scaled_shP_shL);
         pa = pk_cmul_s(pa, w2);  // (w2 and the stride are wave-uniform: straight from SGPRs, not copied into VGPRs every trip)
         asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfA) : "s"(stride));
         if (NCH == 2) asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfB) : "s"(stride));
@@ -1557,7 +1620,8 @@ __device__ __forceinline__ void run_segment_runs(const JobCtx& c, const float2* 
 
 // KC: the whole code is staged behind a MARGIN-entry guard band (c.k_off == MC_MARGIN) at LDS address 0: look-ups use a constant offset
 // PAIRK: zero-shift-prompt E/P/L jobs read their early tap next to the late one (the caller checked the job: mcorr_pair_eligible, multicorrelator.h)
-template <int NT, int MODE, bool WRAP, bool ZP = false, bool AUX = false, bool KC = false, bool PAIRK = false>
+// HALFK: and their shifts are exactly -0.5 / 0 / +0.5 chip, the doubled table in front of `tab` (mcorr_half_chip_eligible, multicorrelator.h)
+template <int NT, int MODE, bool WRAP, bool ZP = false, bool AUX = false, bool KC = false, bool PAIRK = false, bool HALFK = false>
 __device__ __forceinline__ void run_segment(const JobCtx& c, const float2* __restrict__ base, const float* __restrict__ tab,
     const float (&sh)[NT], const int (&rot)[NT], float2 (&acc)[NT], float2* acc_aux = nullptr)
 {
@@ -1588,10 +1652,11 @@ __device__ __forceinline__ void run_segment(const JobCtx& c, const float2* __res
             if constexpr (PAIRK && NT == 3 && ZP && !AUX && PF == 1)
                 {
                     // early read next to late (packed_trip); the caller vouches for the job: shifts exactly one chip apart, code running forward
-                    run_segment_packed<NT, ZP, AUX, NCH, PF, true, KC, MRG>(c, base, tab, sh, acc, acc_aux);
+                    static_assert(!HALFK || (KC && NCH == 2 && !MRG), "half-chip taps: whole-code table, two chunks per trip, four accumulator sets");
+                    run_segment_packed<NT, ZP, AUX, NCH, PF, true, KC, MRG, HALFK>(c, base, tab, sh, acc, acc_aux);
                     return;
                 }
-            run_segment_packed<NT, ZP, AUX, NCH, PF, false, KC, MRG>(c, base, tab, sh, acc, acc_aux);
+            run_segment_packed<NT, ZP, AUX, NCH, PF, false, KC && !HALFK, MRG>(c, base, tab, sh, acc, acc_aux);  // (HALFK: `tab` is not at LDS address 0)
             return;
         }
 #endif

@@ -14,6 +14,14 @@ __host__ __device__ inline bool mcorr_pair_eligible(int n_taps, const float* shi
     return n_taps == 3 && mode == 0 && shifts[1] == 0.0f && (static_cast<double>(shifts[2]) - static_cast<double>(shifts[0]) == 1.0) && code_step > 0.0f;
 }
 
+// a pair-eligible job whose three taps may all be taken from the prompt tap's index chain (mcorr_device.h packed_trip, half-chip taps): early and late exactly half a
+// chip either side of the prompt, and a code short enough that every index of its doubled table, floor(2 w), is a half-precision bit pattern (below 2048)
+constexpr int MCORR_HALF_MAX_CODE_LEN = 1024;
+__host__ __device__ inline bool mcorr_half_chip_eligible(int n_taps, const float* shifts, float code_step, int mode, int code_len)
+{
+    return mcorr_pair_eligible(n_taps, shifts, code_step, mode) && shifts[0] == -0.5f && shifts[2] == 0.5f && code_len <= MCORR_HALF_MAX_CODE_LEN;
+}
+
 struct McorrArgs
 {
     const float2* stream;            // device, complex64 IF samples
@@ -35,6 +43,7 @@ struct McorrArgs
     int fac;                         // 1: the carrier seeds come from the work-group's factor table (default); 0: two evaluations per lane (A/B runs, GSH_MC_FAC=0)
     int pair;                        // 1: every job with two or three taps in this batch is an E/P/L set with a zero-shift prompt, early and late exactly one chip
                                      // apart and the code running forward (the host checked): the 3-tap launch reads early next to late (mcorr_device.h)
+    int half;                        // 1: and every one of them is mcorr_half_chip_eligible: the whole-code 3-tap launch takes its three taps from one index chain
     const int* aux;                  // device, n_jobs, or nullptr.  aux[j] >= 0: job j also computes the single tap of job aux[j] (same window and
                                      // NCO, another code) and writes its output row; -2: job j is computed by its leader; -1: plain job
 };
@@ -64,6 +73,8 @@ int mcorr_launch_classes_t128(const McorrArgs& args, const McorrClassPlan& plan,
 
 // dynamic LDS bytes the kernel needs for a code of max_code_len samples
 size_t mcorr_lds_bytes(int max_code_len);
+// the same for the half-chip flavour of the E/P/L kernels (a doubled table in front); 0: the code is too long for that flavour
+size_t mcorr_lds_bytes_half(int max_code_len);
 // the same when only `window_floats` code samples are staged per work-group
 size_t mcorr_lds_bytes_window(int window_floats);
 // LDS bytes with room for the fused correlator's second code table (aux != nullptr)

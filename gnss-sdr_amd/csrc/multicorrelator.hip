@@ -56,10 +56,13 @@ constexpr int MC_RUN_LEN = GSH_MC_RUN_LEN;  // samples per lane run of the run-b
 // WIN: the launch stages per-segment windows of the codes (a.window_floats > 0); otherwise every work-group stages its whole code at the start of the
 // LDS and the look-ups use a constant offset
 // PAIR: every job of the launch is pair_eligible (the host checked, a.pair): the early tap is read next to the late one
-template <int NT, int MODE, bool AUX, bool RUNS = false, bool WIN = false, bool PAIR = false>
+// HALF: and its shifts are exactly -0.5 / 0 / +0.5 chip, its code at most MC_HALF_MAX_CODE_LEN long (a.half): all three taps from the prompt's index chain
+//       and a doubled code table at the start of the LDS, the plain table behind it (mcorr_device.h packed_trip)
+template <int NT, int MODE, bool AUX, bool RUNS = false, bool WIN = false, bool PAIR = false, bool HALF = false>
 __global__ __launch_bounds__(MC_THREADS, ((NT <= 3 && !AUX) ? GSH_MC_MIN_WAVES : 1)) void mcorr_kernel(McorrArgs a)
 {
     static_assert(!PAIR || (NT == 3 && MODE == 0 && !AUX && !RUNS), "paired taps: the plain E/P/L launch");
+    static_assert(!HALF || (PAIR && !WIN), "half-chip taps: a paired-tap launch with whole-code tables");
     static_assert(!RUNS || (MODE == 0 && !AUX), "the run-based path exists for the standard mode without a fused tap");
     extern __shared__ __align__(16) float lds[];
     const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -138,12 +141,13 @@ __global__ __launch_bounds__(MC_THREADS, ((NT <= 3 && !AUX) ? GSH_MC_MIN_WAVES :
     // ---- stage the local code in LDS: the whole code (+ guard bands holding the wrapped neighbours), or -- when the host found that
     // every segment of this launch touches only a short run of it (long codes, split windows) -- just the samples lo..hi, so that a
     // 10 230-chip code does not cost 41 KB of LDS per work-group and with it most of the compute unit's occupancy
-    float* tab = lds;
+    float* tab = lds + (HALF ? MC_HALF_WORDS : 0);
     const float* __restrict__ gcode = a.codes + static_cast<size_t>(J.code_slot) * a.code_stride;
     bool windowed = false, misfit = false, aux_fast = true;
     int lds_floats;
     typedef const __attribute__((address_space(3))) float* lds_float_ptr;
-    const bool pair_ok = !PAIR || gsh::mcorr_pair_eligible(J.n_taps, J.shifts_chips, J.code_phase_step_chips, J.high_dyn);
+    const bool pair_ok = (!PAIR || gsh::mcorr_pair_eligible(J.n_taps, J.shifts_chips, J.code_phase_step_chips, J.high_dyn))
+                         && (!HALF || gsh::mcorr_half_chip_eligible(J.n_taps, J.shifts_chips, J.code_phase_step_chips, J.high_dyn, c.code_len));
     if (WIN != (a.window_floats > 0) || !pair_ok || (!WIN && reinterpret_cast<size_t>((lds_float_ptr)lds) != 0))  // (this kernel has no static LDS: the dynamic array starts at 0)
         {
             misfit = (c.n_end > c.n_begin);  // cannot happen: the launcher picks the flavour from the same field; reported as NaN if it does
@@ -168,14 +172,23 @@ __global__ __launch_bounds__(MC_THREADS, ((NT <= 3 && !AUX) ? GSH_MC_MIN_WAVES :
         {
             // the code itself: straight copies (no wrap arithmetic); then the two guard bands, one element per thread of the first wave
             // (the single loop with a wrap per element cost ~150 VALU instructions per wave -- 7 % of everything a wave executes for a 25 000-sample window)
+            // (HALF: every value goes into the doubled table as well, two equal words in one 8-byte store: lds[2 i] = lds[2 i + 1] = tab[i])
             const int tab_len = c.code_len + 2 * MC_MARGIN;
-            for (int j = tid; j < c.code_len; j += MC_THREADS) tab[MC_MARGIN + j] = gcode[j];
+            float2* const dbl = reinterpret_cast<float2*>(lds);
+            for (int j = tid; j < c.code_len; j += MC_THREADS)
+                {
+                    const float v = gcode[j];
+                    tab[MC_MARGIN + j] = v;
+                    if (HALF) dbl[MC_MARGIN + j] = make_float2(v, v);
+                }
             if (tid < 2 * MC_MARGIN)
                 {
                     const int k = tid < MC_MARGIN ? tid - MC_MARGIN : c.code_len + (tid - MC_MARGIN);  // -MARGIN .. -1, len .. len + MARGIN - 1
-                    tab[MC_MARGIN + k] = gcode[wrap_margin(k, c.code_len)];
+                    const float v = gcode[wrap_margin(k, c.code_len)];
+                    tab[MC_MARGIN + k] = v;
+                    if (HALF) dbl[MC_MARGIN + k] = make_float2(v, v);
                 }
-            lds_floats = AUX ? a.code_stride + 2 * MC_MARGIN : tab_len;
+            lds_floats = (AUX ? a.code_stride + 2 * MC_MARGIN : tab_len) + (HALF ? MC_HALF_WORDS : 0);
         }
     // ---- the fused correlator's code (AUX): a second table behind the first
     if (AUX && aux_job >= 0 && !misfit)
@@ -257,9 +270,9 @@ __global__ __launch_bounds__(MC_THREADS, ((NT <= 3 && !AUX) ? GSH_MC_MIN_WAVES :
                         }
                 }
             else if (fast && zp)
-                run_segment<NT, MODE, false, true, AUX, !WIN, PAIR>(c, base, tab, sh, rot, acc, &acc_aux);
+                run_segment<NT, MODE, false, true, AUX, !WIN, PAIR, HALF>(c, base, tab, sh, rot, acc, &acc_aux);
             else if (fast)
-                run_segment<NT, MODE, false, false, AUX, !WIN>(c, base, tab, sh, rot, acc, &acc_aux);
+                run_segment<NT, MODE, false, false, AUX, !WIN && !HALF>(c, base, tab, sh, rot, acc, &acc_aux);  // (constant look-up offsets: the table at LDS address 0)
             else
                 run_segment<NT, MODE, true, false, AUX>(c, base, tab, sh, rot, acc, &acc_aux);
         }
@@ -346,8 +359,9 @@ __global__ __launch_bounds__(256) void mcorr_reduce_partials(const float2* __res
     out[i] = s;
 }
 
+// lds_half: the LDS bytes of the half-chip flavour for this launch's codes (mcorr_lds_bytes_half), 0 when they are too long for it
 template <int NT>
-int launch_nt(const McorrArgs& a, int mode, size_t lds, hipStream_t stream)
+int launch_nt(const McorrArgs& a, int mode, size_t lds, size_t lds_half, hipStream_t stream)
 {
     const dim3 grid(static_cast<unsigned>(a.n_launch) * static_cast<unsigned>(a.splits));
     const dim3 block(MC_THREADS);
@@ -389,6 +403,8 @@ int launch_nt(const McorrArgs& a, int mode, size_t lds, hipStream_t stream)
                         {
                             if (a.window_floats > 0)
                                 hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, true, true>), grid, block, lds, stream, a);
+                            else if (a.half && lds_half > 0)
+                                hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, false, true, true>), grid, block, lds_half, stream, a);
                             else
                                 hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, false, true>), grid, block, lds, stream, a);
                             break;
@@ -445,6 +461,7 @@ int mcorr_fac_default()
 #define mcorr_lds_bytes_window mcorr_lds_bytes_window_t128
 #define mcorr_lds_bytes_fused mcorr_lds_bytes_fused_t128
 #define mcorr_lds_bytes mcorr_lds_bytes_t128
+#define mcorr_lds_bytes_half mcorr_lds_bytes_half_t128
 #define mcorr_launch mcorr_launch_t128
 #define mcorr_launch_classes mcorr_launch_classes_t128
 namespace
@@ -469,6 +486,14 @@ size_t mcorr_lds_bytes(int max_code_len)
     return tab * sizeof(float) + (MC_WAVES * GSH_MAX_TAPS + FAC_ENTRIES) * sizeof(float2);
 }
 
+// the half-chip flavour: the doubled table in front of everything else; 0: the codes are too long for it
+size_t mcorr_lds_bytes_half(int max_code_len)
+{
+    if (max_code_len > MC_HALF_MAX_CODE_LEN) return 0;
+    static_assert(MC_HALF_MAX_CODE_LEN == MCORR_HALF_MAX_CODE_LEN, "the host's eligibility rule and the kernel's table size");
+    return static_cast<size_t>(MC_HALF_WORDS) * sizeof(float) + mcorr_lds_bytes(max_code_len);
+}
+
 #ifdef GSH_MC_VARIANT_128
 }  // namespace
 #else
@@ -480,7 +505,9 @@ bool use_128(const McorrArgs& a, int max_taps, int mode)
         const char* e = std::getenv("GSH_MC_WG");
         return e != nullptr ? std::atoi(e) : 0;
     }();
-    const bool possible = mode == 0 && a.aux == nullptr && a.window_floats == 0 && max_taps >= 2 && max_taps <= 3 && a.packed == 1;
+    // (packed == 3, the A/B switch that turns the paired and half-chip trips off, keeps the work-group size of the launch it is compared with: the order of summation
+    //  depends on it, and tests/test_tracking_half_chip_taps_gpu.py holds the two-wave kernels' fast trips bit-identical to their per-tap trips that way)
+    const bool possible = mode == 0 && a.aux == nullptr && a.window_floats == 0 && max_taps >= 2 && max_taps <= 3 && (a.packed == 1 || a.packed == 3);
     if (!possible || forced == 256) return false;
     if (forced == 128) return true;
     return static_cast<long long>(a.n_launch) * a.splits >= 2 * 2560;
@@ -498,15 +525,16 @@ int mcorr_launch(const McorrArgs& a, int max_taps, int mode, int max_code_len, h
     const size_t lds = a.aux != nullptr ? mcorr_lds_bytes_fused(max_code_len, a.window_floats)
                                         : (a.window_floats > 0 ? mcorr_lds_bytes_window(a.window_floats) : mcorr_lds_bytes(max_code_len));
     GSH_REQUIRE(lds <= 160 * 1024, "local code of %d samples does not fit the 160 KiB LDS", max_code_len);
+    const size_t lds_half = mcorr_lds_bytes_half(max_code_len);
     int rc;
     if (max_taps == 1)
-        rc = launch_nt<1>(a, mode, lds, stream);
+        rc = launch_nt<1>(a, mode, lds, lds_half, stream);
     else if (max_taps <= 3)
-        rc = launch_nt<3>(a, mode, lds, stream);
+        rc = launch_nt<3>(a, mode, lds, lds_half, stream);
     else if (max_taps <= 5)
-        rc = launch_nt<5>(a, mode, lds, stream);
+        rc = launch_nt<5>(a, mode, lds, lds_half, stream);
     else
-        rc = launch_nt<GSH_MAX_TAPS>(a, mode, lds, stream);
+        rc = launch_nt<GSH_MAX_TAPS>(a, mode, lds, lds_half, stream);
     if (rc != GSH_OK) return rc;
     if (a.splits > 1)
         {
@@ -546,20 +574,21 @@ int mcorr_launch_classes(const McorrArgs& args, const McorrClassPlan& plan, int 
             const size_t lds = a.aux != nullptr ? mcorr_lds_bytes_fused(max_code_len, a.window_floats)
                                                 : (a.window_floats > 0 ? mcorr_lds_bytes_window(a.window_floats) : mcorr_lds_bytes(max_code_len));
             GSH_REQUIRE(lds <= 160 * 1024, "local code of %d samples does not fit the 160 KiB LDS", max_code_len);
+            const size_t lds_half = mcorr_lds_bytes_half(max_code_len);
             int rc;
             switch (class_taps[c])
                 {
                 case 1:
-                    rc = launch_nt<1>(a, mode, lds, stream);
+                    rc = launch_nt<1>(a, mode, lds, lds_half, stream);
                     break;
                 case 3:
-                    rc = launch_nt<3>(a, mode, lds, stream);
+                    rc = launch_nt<3>(a, mode, lds, lds_half, stream);
                     break;
                 case 5:
-                    rc = launch_nt<5>(a, mode, lds, stream);
+                    rc = launch_nt<5>(a, mode, lds, lds_half, stream);
                     break;
                 default:
-                    rc = launch_nt<GSH_MAX_TAPS>(a, mode, lds, stream);
+                    rc = launch_nt<GSH_MAX_TAPS>(a, mode, lds, lds_half, stream);
                     break;
                 }
             if (rc != GSH_OK) return rc;

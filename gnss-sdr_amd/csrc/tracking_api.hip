@@ -37,6 +37,7 @@ struct gsh_bank
     // windowed code staging (multicorrelator.hip): possible when every job of the batch is mode 0 with code_step >= 0
     bool window_eligible{false};
     bool pair{false};                   // the staged batch's 2- / 3-tap jobs are all mcorr_pair_eligible (multicorrelator.h)
+    bool half{false};                   // ... and all mcorr_half_chip_eligible: taps at exactly -0.5 / 0 / +0.5 chip, no code of the bank too long
     double win_step_max{0.0};   // largest code_phase_step_chips of the batch (code samples per input sample)
     double win_code_span_max{0.0};  // largest code_phase_step_chips * n_samples of the batch: code samples one window walks
     double win_shift_span{0.0}; // largest (max shift - min shift) of the batch
@@ -154,6 +155,7 @@ int bank_stage_jobs(gsh_bank* b, const gsh_corr_job* jobs, int n_jobs)
     unsigned long long max_end = 0;
     bool window_eligible = (mode == 0);
     bool pair = true;  // every job the 3-tap launch will see may read its early tap next to the late one (multicorrelator.h mcorr_pair_eligible)
+    bool half = true;  // ... and take all three taps from the prompt's index chain (mcorr_half_chip_eligible)
     double step_max = 0.0, shift_span = 0.0, code_span = 0.0;
     for (int i = 0; i < n_jobs; i++)
         {
@@ -161,6 +163,9 @@ int bank_stage_jobs(gsh_bank* b, const gsh_corr_job* jobs, int n_jobs)
             if (rc != GSH_OK) return rc;
             if ((jobs[i].n_taps == 2 || jobs[i].n_taps == 3) && !gsh::mcorr_pair_eligible(jobs[i].n_taps, jobs[i].shifts_chips, jobs[i].code_phase_step_chips, jobs[i].high_dyn))
                 pair = false;
+            if ((jobs[i].n_taps == 2 || jobs[i].n_taps == 3)
+                && !gsh::mcorr_half_chip_eligible(jobs[i].n_taps, jobs[i].shifts_chips, jobs[i].code_phase_step_chips, jobs[i].high_dyn, b->max_code_len))
+                half = false;
             max_samples = std::max(max_samples, jobs[i].n_samples);
             if (!(jobs[i].code_phase_step_chips >= 0.0f)) window_eligible = false;
             step_max = std::max(step_max, static_cast<double>(jobs[i].code_phase_step_chips));
@@ -250,6 +255,7 @@ int bank_stage_jobs(gsh_bank* b, const gsh_corr_job* jobs, int n_jobs)
     b->max_samples = max_samples;
     b->window_eligible = window_eligible;
     b->pair = pair;
+    b->half = pair && half;
     b->win_step_max = step_max;
     b->win_code_span_max = code_span;
     b->win_shift_span = shift_span;
@@ -534,6 +540,7 @@ extern "C"
         a.packed = gsh::mcorr_packed_default();
         a.fac = gsh::mcorr_fac_default();
         a.pair = b->pair ? 1 : 0;
+        a.half = b->half ? 1 : 0;
         a.sample_base = b->sample_base;
         a.ring_capacity = b->ring != nullptr ? b->ring->capacity : 0ull;
         // the second code table must not cost the occupancy the fusion is meant to win: only with windowed tables or short codes
