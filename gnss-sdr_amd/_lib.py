@@ -105,6 +105,13 @@ class TrkConf(C.Structure):
     ]
 
 
+class TrkKfConf(C.Structure):
+    """gsh_trk_kf_conf."""
+    _fields_ = [(n, C.c_double) for n in (
+        "code_disc_sd_chips", "carrier_disc_sd_rads", "code_phase_sd_chips", "carrier_phase_sd_rad", "carrier_freq_sd_hz", "carrier_freq_rate_sd_hz_s",
+        "init_code_phase_sd_chips", "init_carrier_phase_sd_rad", "init_carrier_freq_sd_hz", "init_carrier_freq_rate_sd_hz_s")]
+
+
 class TrkEpoch(C.Structure):
     """gsh_trk_epoch."""
     _fields_ = [
@@ -263,6 +270,8 @@ SYMBOLS = {
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gsh_trk_live_quiesce": (C.c_int, [_P]),
     "gsh_trk_time_run": (C.c_int, [_P, C.c_int, C.c_int, _F]),
+    "gsh_trk_set_kalman": (C.c_int, [_P, C.POINTER(TrkKfConf)]),
+    "gsh_trk_kf_state": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gsh_trk_write_dump": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(TrkConf), C.c_uint32, C.POINTER(TrkEpoch), C.c_int, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint32)]),
     "gsh_acq_create": (C.c_int, [C.c_int, C.POINTER(AcqConf), C.POINTER(_P)]),

@@ -22,6 +22,7 @@
 #endif
 #define GSH_MC_THREADS GSH_TRK_THREADS
 #include "exact_division.h"
+#include "kalman_step.h"
 #include "mcorr_device.h"
 #include "sample_stream.h"
 #include <algorithm>
@@ -238,6 +239,15 @@ struct LiveShared  // the live form's own words in LDS (the launched form has no
     int pad_;
 };
 struct NoLiveShared
+{
+};
+// the Kalman flavour's own block in LDS (the other flavours have none of it: their LDS layout, and with it their register allocation, stay what they were)
+struct KfShared
+{
+    KfState st;  // the channel's filter, staged from / returned to its block in device memory (gsh_trk::d_kf)
+    KfWork w;    // the step's intermediates
+};
+struct NoKfShared
 {
 };
 
@@ -793,11 +803,15 @@ __device__ __forceinline__ unsigned conf_switches(const gsh_trk_conf& c)
 // HD: Dll_Pll_Conf::high_dyn -- a compile-time switch so that the standard path does not carry the high-dynamics correlator's registers
 // LIVE: the residency form of the loop (gsh_trk_live_*) -- a compile-time switch as well: the launched form keeps the code (and the registers) it had
 // COOP (round 6, gsh_trk_set_split): a.coop_g work-groups on different compute units share every window of a channel -- see the block comment at `coop` below
-template <int NT, bool HD, bool LIVE, bool COOP = false>
+// KF (gsh_trk_set_kalman): kf_tracking's loop -- the carrier and code lanes stop at their discriminators, the join runs csrc/kalman_step.h and the Kalman form of
+// update_tracking_vars; correlation, symbol synchronisation, coherent accumulation, lock detectors, records and publish are the other flavours'.  Launched runs of
+// one work-group per channel only: instantiated for NT = 3 and 5.
+template <int NT, bool HD, bool LIVE, bool COOP = false, bool KF = false>
 // conf: the device copy of the configuration as a parameter of its own, const and __restrict__: nothing the kernel writes aliases it, so its fields are
 // fetched with scalar loads and may be hoisted -- through the pointer inside TrkArgs every c.field in thread 0's section was a vector memory load that could not
 // move above the record stores before it.
-__global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const gsh_trk_conf* __restrict__ conf)
+// kfs: the channels' Kalman blocks (KF flavours; nullptr and never looked at otherwise)
+__global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const gsh_trk_conf* __restrict__ conf, KfState* __restrict__ kfs)
 {
     extern __shared__ __align__(16) float lds[];
     __shared__ NextWindow win;
@@ -818,6 +832,9 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
     static_assert(sizeof(gsh_trk_epoch) % 8 == 0 && sizeof(gsh_trk_epoch) / 8 <= 64, "the record is written out as 8-byte pieces by one wave");
     static_assert(sizeof(TrkChannel) % 4 == 0 && sizeof(LockState) % 4 == 0, "state is copied as 32-bit words");
     static_assert(!COOP || (!HD && !LIVE), "cooperating work-groups exist for the launched standard-mode loop");
+    static_assert(!KF || (!HD && !LIVE && !COOP), "the Kalman flavour exists for launched standard-mode runs of one work-group per channel");
+    __shared__ __align__(16) std::conditional_t<KF, KfShared, NoKfShared> kf;
+    static_assert(sizeof(KfState) % 4 == 0, "state is copied as 32-bit words");
     // COOP: block b sits on XCD b % 8; the coop_g work-groups of a channel take consecutive slots of ONE XCD (a hand-off between them is an L2 round trip: ~350 ns,
     // profiles/ubench/pingpong.hip), channel = (slot / coop_g) * 8 + xcd
     int ch = blockIdx.x, coop_rank = 0;
@@ -841,6 +858,12 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
         unsigned* ll = reinterpret_cast<unsigned*>(&lk);
         for (int i = tid; i < static_cast<int>(sizeof(TrkChannel) / 4); i += MC_THREADS) ls[i] = gs[i];
         for (int i = tid; i < static_cast<int>(sizeof(LockState) / 4); i += MC_THREADS) ll[i] = gl[i];
+        if constexpr (KF)
+            {
+                const unsigned* gk = reinterpret_cast<const unsigned*>(kfs + ch);
+                unsigned* lkf = reinterpret_cast<unsigned*>(&kf.st);
+                for (int i = tid; i < static_cast<int>(sizeof(KfState) / 4); i += MC_THREADS) lkf[i] = gk[i];
+            }
     }
     __syncthreads();
     const int code_len = s.code_len;
@@ -1406,7 +1429,7 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                             // the carrier filter's state and the previous prompt come out of LDS in one go, up front (pinned by the asm: see the note at join_and_update)
                             FllPllState pl = s.pll;
                             float p_old_re = s.p_old_re, p_old_im = s.p_old_im;
-                            if constexpr (!HD)  // (the high-dynamics flavours sit at the register limit: thirteen more live values there are scratch)
+                            if constexpr (!HD && !KF)  // (the high-dynamics flavours sit at the register limit: thirteen more live values there are scratch)
                                 asm volatile("" : "+v"(pl.w), "+v"(pl.x), "+v"(pl.w0p), "+v"(pl.w0p2), "+v"(pl.w0p3), "+v"(pl.w0f), "+v"(pl.w0f2), "+v"(pl.a2), "+v"(pl.a3), "+v"(pl.b3),
                                              "+v"(pl.order), "+v"(p_old_re), "+v"(p_old_im));
                             if (run_state == 3 || run_state == 4)
@@ -1440,6 +1463,9 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                                     const bool cloop_now = CF(CF_SYMBOL_SYNC) ? (lk.cloop != 0) : CF(CF_CLOOP);
                                     const double corr_time = (CF(CF_SYMBOL_SYNC) && lk.corr_time > 0.0) ? lk.corr_time : code_period;  // d_current_correlation_time_s
                                     carr_phase_error_hz = div_by_constant_if<GSH_TRK_FAST_DIV != 0>(cloop_now ? pll_cloop_two_quadrant_atan_d(P) : pll_four_quadrant_atan_d(P), GNSS_TWO_PI_D, INV_TWO_PI_D);  // (a float arctangent: zero, or no smaller than 1e-45)
+                                    // (Kalman flavour: run_Kf's carrier discriminator, kf.cc:1146-1155 -- the same two lines -- and nothing else on this lane)
+                                    if constexpr (!KF)
+                                    {
                                     float carr_error_filt;
                                     if ((pull_in && CF(CF_FLL_PULL_IN)) || CF(CF_FLL_STEADY))
                                         {
@@ -1462,6 +1488,7 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                                     s.pll.x = pl.x;
                                     carr_error_filt_hz = carr_error_filt;
                                     s.carrier_doppler_hz = carr_error_filt_hz;
+                                    }
                                 }
                         }
                     else if (tid == 64)
@@ -1475,7 +1502,8 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                                         code_error_chips = dll_nc_vemlp_normalized_d(acc[0], acc[1], acc[NT - 2], acc[NT - 1]);
                                     else
                                         code_error_chips = dll_nc_e_minus_l_normalized_d(E, L, spc_now, c.slope, c.y_intercept);
-                                    code_error_filt_chips = loop_filter_apply<!HD>(s.dll, static_cast<float>(code_error_chips));
+                                    if constexpr (!KF)  // (Kalman flavour: run_Kf's code discriminator, kf.cc:1157-1165; d_code_error_kf_chips comes from the join)
+                                        code_error_filt_chips = loop_filter_apply<!HD>(s.dll, static_cast<float>(code_error_chips));
                                 }
                             mail.code_error_chips = code_error_chips;
                             mail.code_error_filt_chips = code_error_filt_chips;
@@ -1487,7 +1515,7 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                                 {
                                     gsh_trk_epoch& r = rec_ref();
                                     rec_set<LIVE>(r.code_error_chips, code_error_chips);
-                                    rec_set<LIVE>(r.code_error_filt_chips, code_error_filt_chips);
+                                    if constexpr (!KF) rec_set<LIVE>(r.code_error_filt_chips, code_error_filt_chips);
                                 }
                         }
                     else
@@ -1661,6 +1689,26 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                     // (the asm below pins the reads there -- the compiler, scheduling for few live values, had put every read in front of its first use: a dozen
                     // LDS round trips on the one lane the work-group waits for), what it changes goes back in one go, and the record and the next window are formed
                     // from the registers (they used to re-read what had just been written).
+                    // Kalman flavour: update_kf_cn0 (state 4) and run_Kf's filter, kf.cc:1973-1974, 1168-1217, out of the channel's block in LDS -- in front of the
+                    // register copies below, so that the step's live values and theirs do not add up
+                    double kf_code_error_chips = 0.0, kf_carrier_phase_rad = 0.0, kf_doppler_hz = 0.0, kf_doppler_rate_hz_s = 0.0;
+                    if constexpr (KF)
+                        {
+                            if (run_state != 3)
+                                {
+                                    if (run_state == 4)
+                                        {
+                                            // R from THIS period's d_CN0_SNV_dB_Hz: the C/N0 lane's word of the period (the other flavours meet that lane only at the barrier
+                                            // that ends the period, or when a fail counter can pass its limit)
+                                            if (flag_join) lane_waits(mail.cn0_seq, seq);
+                                            kf_cn0(kf.st, lk.spc_now, static_cast<double>(lk.cn0_db_hz));
+                                        }
+                                    kf_code_error_chips = kf_run(kf.st, kf.w, mail.code_error_chips, carr_phase_error_hz);
+                                    kf_carrier_phase_rad = kf.st.x[1];
+                                    kf_doppler_hz = kf.st.x[2];
+                                    kf_doppler_rate_hz_s = kf.st.x[3];
+                                }
+                        }
                     double st_code_freq = s.code_freq_chips, st_rem_code_samples = s.rem_code_phase_samples, st_acc_phase = s.acc_carrier_phase_rad;
                     double st_doppler = s.carrier_doppler_hz, st_phase_rate = s.carrier_phase_rate_step_rad, st_code_rate = s.code_phase_rate_step_chips;
                     float st_rem_carr = s.rem_carr_phase_rad;
@@ -1776,7 +1824,35 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                     st_rem_code_samples = k_blk - static_cast<double>(prn_len);
                     st_rem_code_chips = div_by_constant_if<FAST>(st_code_freq * st_rem_code_samples, k_fs_in, a.inv_fs_in);
                     };
-                    if (a.inv_fs_in != 0.0)
+                    // The Kalman flavour's join (the end of run_Kf, kf.cc:1187-1215) and update_tracking_vars (kf.cc:1251-1327): plain divisions as written there, no
+                    // front-end frequency offset (kf_tracking has none, :1265), and d_rem_carr_phase_rad -- a float (kf_tracking.h:204) -- takes the filter's
+                    // unbounded carrier phase narrowed to float BEFORE the remnant is added and the sum is wrapped
+                    auto kf_join_and_update = [&]() {
+                        if (run_state != 3)
+                            {
+                                st_doppler = kf_doppler_hz;                                                      // d_carrier_doppler_kf_hz, :1191
+                                st_code_freq = k_chip_rate + st_doppler * k_chip_rate / k_carrier_freq;          // d_code_freq_kf_chips_s, :1201
+                                st_rem_code_samples += k_fs_in * kf_code_error_chips / st_code_freq;             // :1214
+                                st_rem_carr = static_cast<float>(kf_carrier_phase_rad);                          // :1215
+                            }
+                        const double t_chip = 1.0 / st_code_freq;
+                        const double t_prn = t_chip * static_cast<double>(k_code_length);
+                        const double t_prn_samples = t_prn * k_fs_in;
+                        const double k_blk = t_prn_samples + st_rem_code_samples;
+                        prn_len = static_cast<int>(floor(k_blk));
+                        st_phase_step = GNSS_TWO_PI_D * st_doppler / k_fs_in;  // :1265
+                        const float remnant = static_cast<float>(st_phase_step * static_cast<double>(prn_len) +
+                                                                 0.5 * st_phase_rate * static_cast<double>(prn_len) * static_cast<double>(prn_len));  // :1292-1293 (the rate is 0: no high_dyn)
+                        st_rem_carr += remnant;
+                        st_rem_carr = static_cast<float>(fmod(static_cast<double>(st_rem_carr), GNSS_TWO_PI_D));
+                        st_acc_phase -= remnant;  // :1297: the float remnant, not the double product
+                        st_code_step = st_code_freq / k_fs_in;
+                        st_rem_code_samples = k_blk - static_cast<double>(prn_len);
+                        st_rem_code_chips = st_code_freq * st_rem_code_samples / k_fs_in;
+                    };
+                    if constexpr (KF)
+                        kf_join_and_update();
+                    else if (a.inv_fs_in != 0.0)
                         join_and_update(std::true_type{});
                     else
                         join_and_update(std::false_type{});
@@ -1907,6 +1983,13 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                                                     lk.narrow = 1;
                                                     st_narrow = 1;
                                                     lk.spc_now = c.early_late_space_narrow_chips;
+                                                    if constexpr (KF)
+                                                        {
+                                                            // update_kf_narrow_integration_time, kf.cc:1891: called before d_trk_parameters.spc narrows (:1899, 1911), with
+                                                            // this period's d_CN0_SNV_dB_Hz
+                                                            if (flag_join) lane_waits(mail.cn0_seq, seq);
+                                                            kf_narrow_integration_time(kf.st, kf.w, extend, lk.corr_time, c.spc, static_cast<double>(lk.cn0_db_hz));
+                                                        }
                                                 }
                                             else
                                                 {
@@ -1948,8 +2031,17 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                             rec_set<LIVE>(r.carrier_doppler_hz, st_doppler);
                             rec_set<LIVE>(r.code_freq_chips, st_code_freq);
                             rec_set<LIVE>(r.carr_phase_error_hz, carr_phase_error_hz);
+                            if constexpr (KF)  // what kf_tracking::log_data puts into these slots (kf.cc:1443-1539): Doppler rate, Doppler, d_code_error_kf_chips
+                                {
+                                    rec_set<LIVE>(r.carr_freq_error_hz, kf_doppler_rate_hz_s);
+                                    rec_set<LIVE>(r.carr_error_filt_hz, kf_doppler_hz);
+                                    rec_set<LIVE>(r.code_error_filt_chips, kf_code_error_chips);
+                                }
+                            else
+                                {
                             rec_set<LIVE>(r.carr_freq_error_hz, carr_freq_error_hz);
                             rec_set<LIVE>(r.carr_error_filt_hz, carr_error_filt_hz);
+                                }
                             rec_set<LIVE>(r.rem_code_phase_samples, st_rem_code_samples);
                             rec_set<LIVE>(r.acc_carrier_phase_rad, st_acc_phase);
 #ifdef GSH_TRK_PROFILE
@@ -1976,6 +2068,7 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
                     s.acc_carrier_phase_rad = st_acc_phase;
                     s.rem_carr_phase_rad = st_rem_carr;
                     s.pos = new_pos;
+                    if constexpr (KF) s.carrier_doppler_hz = st_doppler;  // (the other flavours' carrier lane writes it)
                     if (HD)
                         {
                             s.carrier_phase_rate_step_rad = st_phase_rate;
@@ -2059,6 +2152,12 @@ __global__ __launch_bounds__(MC_THREADS) void trk_loop_kernel(TrkArgs a, const g
         asm volatile("" : "+v"(t2));
         for (int i = t2; i < static_cast<int>(sizeof(TrkChannel) / 4); i += MC_THREADS) gs[i] = ls[i];
         for (int i = t2; i < static_cast<int>(sizeof(LockState) / 4); i += MC_THREADS) gl[i] = ll[i];
+        if constexpr (KF)
+            {
+                unsigned* gk = reinterpret_cast<unsigned*>(kfs + ch);
+                const unsigned* lkf = reinterpret_cast<const unsigned*>(&kf.st);
+                for (int i = t2; i < static_cast<int>(sizeof(KfState) / 4); i += MC_THREADS) gk[i] = lkf[i];
+            }
     }
     if (tid == 0)
         {
@@ -2235,6 +2334,11 @@ struct gsh_trk
     int split{1};                                   // work-groups per channel
     unsigned long long* d_coop{nullptr};            // n_channels * coop_stride(split) + 1 tagged words (TrkArgs::coop_box)
     unsigned coop_seq{1};                           // tag of the next launch's first window
+    // ---- Kalman-filter loop (gsh_trk_set_kalman): launched runs of one work-group per channel only
+    bool kalman{false};
+    gsh_trk_kf_conf kf{};
+    gsh::KfState* d_kf{nullptr};                    // n_channels: the filters, device-owned between launches like d_chan
+    gsh::KfState* d_kf_backup{nullptr};
 };
 
 namespace
@@ -2336,23 +2440,33 @@ int trk_launch(gsh_trk* t, int n_epochs, gsh_trk_epoch* d_records, gsh::TrkTail*
     if (coop) t->coop_seq += static_cast<unsigned>(n_epochs) + 2u;  // (tags never repeat within 2^32 periods)
     const dim3 grid(coop ? static_cast<unsigned>((t->n_channels + 7) / 8 * 8 * t->split) : static_cast<unsigned>(t->n_channels)), block(gsh::mcdev::MC_THREADS);
     hipStream_t st = live != nullptr ? t->live_stream : t->stream;
-    if (coop)
+    gsh::KfState* const no_kf = nullptr;
+    if (t->kalman)
+        {
+            // (gsh_trk_set_kalman has refused high_dyn and a split; gsh_trk_live_begin refuses a Kalman handle)
+            if (live != nullptr || coop || t->conf.high_dyn || t->d_kf == nullptr) return set_error(GSH_ERR_STATE, "the Kalman loop runs launched, one work-group per channel");
+            if (t->conf.veml)
+                hipLaunchKernelGGL((gsh::trk_loop_kernel<5, false, false, false, true>), grid, block, lds, st, a, a.conf, t->d_kf);
+            else
+                hipLaunchKernelGGL((gsh::trk_loop_kernel<3, false, false, false, true>), grid, block, lds, st, a, a.conf, t->d_kf);
+        }
+    else if (coop)
         {
             if (t->conf.veml)
-                hipLaunchKernelGGL((gsh::trk_loop_kernel<5, false, false, true>), grid, block, lds, st, a, a.conf);
+                hipLaunchKernelGGL((gsh::trk_loop_kernel<5, false, false, true>), grid, block, lds, st, a, a.conf, no_kf);
             else
-                hipLaunchKernelGGL((gsh::trk_loop_kernel<3, false, false, true>), grid, block, lds, st, a, a.conf);
+                hipLaunchKernelGGL((gsh::trk_loop_kernel<3, false, false, true>), grid, block, lds, st, a, a.conf, no_kf);
         }
     else
     {
-        using KernelFn = void (*)(gsh::TrkArgs, const gsh_trk_conf*);
+        using KernelFn = void (*)(gsh::TrkArgs, const gsh_trk_conf*, gsh::KfState*);
         const bool L = live != nullptr;
         KernelFn fn;
         if (t->conf.veml)
             fn = t->conf.high_dyn ? (L ? gsh::trk_loop_kernel<5, true, true> : gsh::trk_loop_kernel<5, true, false>) : (L ? gsh::trk_loop_kernel<5, false, true> : gsh::trk_loop_kernel<5, false, false>);
         else
             fn = t->conf.high_dyn ? (L ? gsh::trk_loop_kernel<3, true, true> : gsh::trk_loop_kernel<3, true, false>) : (L ? gsh::trk_loop_kernel<3, false, true> : gsh::trk_loop_kernel<3, false, false>);
-        hipLaunchKernelGGL(fn, grid, block, lds, st, a, a.conf);
+        hipLaunchKernelGGL(fn, grid, block, lds, st, a, a.conf, no_kf);
     }
     GSH_HIP(hipGetLastError());
     if (live == nullptr && t->ring != nullptr)
@@ -2659,6 +2773,8 @@ extern "C"
         if (t->d_records) (void)hipFree(t->d_records);
         if (t->d_tail) (void)hipFree(t->d_tail);
         if (t->d_coop) (void)hipFree(t->d_coop);
+        if (t->d_kf) (void)hipFree(t->d_kf);
+        if (t->d_kf_backup) (void)hipFree(t->d_kf_backup);
         if (t->d_conf) (void)hipFree(t->d_conf);
         if (t->h_records) (void)hipHostFree(t->h_records);
         if (t->h_tail) (void)hipHostFree(t->h_tail);
@@ -2820,6 +2936,7 @@ extern "C"
         // start_tracking, trk.cc:803-826, and the pull-in state, :1956-1958
         s.carrier_doppler_hz = acq_carrier_doppler_hz;
         s.carrier_phase_step_rad = gsh::GNSS_TWO_PI_D * (s.carrier_doppler_hz + c.cfo_frequency_hz) / c.fs_in;  // trk.cc:801, :1003
+        if (t->kalman) s.carrier_phase_step_rad = gsh::GNSS_TWO_PI_D * s.carrier_doppler_hz / c.fs_in;           // kf_tracking::start_tracking has no offset term
         s.code_freq_chips = c.code_chip_rate;
         s.code_phase_step_chips = s.code_freq_chips / c.fs_in;
         s.rem_code_phase_samples = 0.0;
@@ -2892,6 +3009,15 @@ extern "C"
         lk.state = 2;            // pull-in hands over to state 2 (trk.cc:1963)
         lk.cloop = c.cloop;      // d_cloop = true at start_tracking (trk.cc:1072); conf.cloop lets a caller start four-quadrant
         GSH_HIP(hipMemcpyAsync(t->d_lock + channel, &lk, sizeof(lk), hipMemcpyHostToDevice, t->stream));
+        gsh::KfState kfs{};
+        if (t->kalman)
+            {
+                // init_kf(0.0, d_carrier_doppler_kf_hz) at the end of the pull-in, kf.cc:1772, with d_current_correlation_time_s = d_code_period (:853)
+                const double sd[10] = {t->kf.code_disc_sd_chips, t->kf.carrier_disc_sd_rads, t->kf.code_phase_sd_chips, t->kf.carrier_phase_sd_rad, t->kf.carrier_freq_sd_hz,
+                    t->kf.carrier_freq_rate_sd_hz_s, t->kf.init_code_phase_sd_chips, t->kf.init_carrier_phase_sd_rad, t->kf.init_carrier_freq_sd_hz, t->kf.init_carrier_freq_rate_sd_hz_s};
+                gsh::kf_init(kfs, sd, gsh::kf_beta(c.code_chip_rate, c.signal_carrier_freq), code_period, 0.0, acq_carrier_doppler_hz);
+                GSH_HIP(hipMemcpyAsync(t->d_kf + channel, &kfs, sizeof(kfs), hipMemcpyHostToDevice, t->stream));
+            }
         GSH_HIP(hipStreamSynchronize(t->stream));
         return GSH_OK;
     }
@@ -3022,6 +3148,7 @@ extern "C"
         if (t->pending_epochs >= 0) return set_error(GSH_ERR_STATE, "gsh_trk_set_split: a run has been begun and not ended");
         GSH_HIP(hipSetDevice(t->device));
         if (live_reap(t) != 0) return set_error(GSH_ERR_STATE, "gsh_trk_set_split: a live residency is in flight (gsh_trk_live_quiesce first)");
+        GSH_REQUIRE(!t->kalman || work_groups_per_channel == 1, "the Kalman loop (gsh_trk_set_kalman) runs one work-group per channel: split %d", work_groups_per_channel);
         if (work_groups_per_channel == 0)
             {
                 // by the window's length in trips and the compute units the channels leave free (measured, profiles/ab/r06/session17.txt: 7 trips -- 25 000 samples,
@@ -3071,6 +3198,7 @@ extern "C"
     int gsh_trk_live_begin(gsh_trk_t* t)
     {
         GSH_REQUIRE(t != nullptr, "null handle");
+        GSH_REQUIRE(!t->kalman, "the Kalman loop (gsh_trk_set_kalman) has no live residencies: launched runs only");
         if (t->ring == nullptr) return set_error(GSH_ERR_STATE, "live mode follows a sample ring (gsh_trk_set_stream_ring)");
         if (t->pending_epochs >= 0) return set_error(GSH_ERR_STATE, "gsh_trk_live_begin: a run has been begun and not ended");
         GSH_HIP(hipSetDevice(t->device));
@@ -3169,6 +3297,65 @@ extern "C"
         return live_quiesce(t);
     }
 
+    int gsh_trk_set_kalman(gsh_trk_t* t, const gsh_trk_kf_conf* kf)
+    {
+        GSH_REQUIRE(t != nullptr, "null handle");
+        if (kf != nullptr)
+            {
+                const gsh_trk_conf& c = t->conf;
+                GSH_REQUIRE(!c.high_dyn, "the Kalman loop does not model high_dyn (the smoother that overwrites the Doppler rate, kf_tracking.cc:1269-1291)");
+                GSH_REQUIRE(!c.enable_doppler_correction, "kf_tracking has no Doppler correction (enable_doppler_correction)");
+                GSH_REQUIRE(t->split == 1, "the Kalman loop runs one work-group per channel: gsh_trk_set_split(1) first (split %d)", t->split);
+                GSH_REQUIRE(!c.enable_symbol_sync || c.enable_lock_detectors, "the Kalman loop with enable_symbol_sync needs enable_lock_detectors: state 4 rebuilds R from the C/N0 estimate");
+                const double sd[10] = {kf->code_disc_sd_chips, kf->carrier_disc_sd_rads, kf->code_phase_sd_chips, kf->carrier_phase_sd_rad, kf->carrier_freq_sd_hz,
+                    kf->carrier_freq_rate_sd_hz_s, kf->init_code_phase_sd_chips, kf->init_carrier_phase_sd_rad, kf->init_carrier_freq_sd_hz, kf->init_carrier_freq_rate_sd_hz_s};
+                for (int i = 0; i < 10; i++) GSH_REQUIRE(std::isfinite(sd[i]) && sd[i] >= 0.0, "standard deviation %d of gsh_trk_kf_conf is %g (finite and not negative)", i, sd[i]);
+            }
+        if (t->pending_epochs >= 0) return set_error(GSH_ERR_STATE, "gsh_trk_set_kalman: a run has been begun and not ended");
+        GSH_HIP(hipSetDevice(t->device));
+        if (live_reap(t) != 0) return set_error(GSH_ERR_STATE, "gsh_trk_set_kalman: a live residency is in flight (gsh_trk_live_quiesce first)");
+        live_refresh_host_state(t);
+        for (const auto& ch : t->h_chan)
+            if (ch.active) return set_error(GSH_ERR_STATE, "gsh_trk_set_kalman: a channel is active (only while no channel is started)");
+        if (kf == nullptr)
+            {
+                t->kalman = false;
+                return GSH_OK;
+            }
+        if (t->d_kf == nullptr)
+            {
+                const size_t bytes = sizeof(gsh::KfState) * static_cast<size_t>(t->n_channels);
+                GSH_HIP(hipMalloc(&t->d_kf, bytes));
+                GSH_HIP(hipMalloc(&t->d_kf_backup, bytes));
+                GSH_HIP(hipMemset(t->d_kf, 0, bytes));
+                if (trk_lds_bytes(t) > 64 * 1024)
+                    {
+                        const int lds = static_cast<int>(trk_lds_bytes(t));
+                        GSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gsh::trk_loop_kernel<3, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                        GSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gsh::trk_loop_kernel<5, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                    }
+            }
+        t->kf = *kf;
+        t->kalman = true;
+        return GSH_OK;
+    }
+
+    int gsh_trk_kf_state(gsh_trk_t* t, int channel, double x[4], double P[16], double R[2])
+    {
+        GSH_REQUIRE(t != nullptr, "null handle");
+        GSH_REQUIRE(channel >= 0 && channel < t->n_channels, "channel %d outside 0..%d", channel, t->n_channels - 1);
+        if (!t->kalman || t->d_kf == nullptr) return set_error(GSH_ERR_STATE, "gsh_trk_kf_state: not a Kalman handle (gsh_trk_set_kalman)");
+        if (t->pending_epochs >= 0) return set_error(GSH_ERR_STATE, "gsh_trk_kf_state: a run has been begun and not ended");
+        GSH_HIP(hipSetDevice(t->device));
+        gsh::KfState s{};
+        GSH_HIP(hipMemcpyAsync(&s, t->d_kf + channel, sizeof(s), hipMemcpyDeviceToHost, t->stream));
+        GSH_HIP(hipStreamSynchronize(t->stream));
+        if (x != nullptr) std::memcpy(x, s.x, sizeof(s.x));
+        if (P != nullptr) std::memcpy(P, s.P, sizeof(s.P));
+        if (R != nullptr) std::memcpy(R, s.R, sizeof(s.R));
+        return GSH_OK;
+    }
+
     int gsh_trk_run(gsh_trk_t* t, int n_epochs, gsh_trk_epoch* records, int32_t* epochs_done)
     {
         int rc = gsh_trk_run_begin(t, n_epochs, records != nullptr ? 1 : 0);
@@ -3197,6 +3384,8 @@ extern "C"
         const size_t lbytes = sizeof(gsh::LockState) * t->n_channels;
         GSH_HIP(hipMemcpyAsync(t->d_chan_backup, t->d_chan, bytes, hipMemcpyDeviceToDevice, t->stream));
         GSH_HIP(hipMemcpyAsync(t->d_lock_backup, t->d_lock, lbytes, hipMemcpyDeviceToDevice, t->stream));
+        const size_t kbytes = t->kalman ? sizeof(gsh::KfState) * t->n_channels : 0;  // the Kalman filters are loop state like the rest
+        if (kbytes) GSH_HIP(hipMemcpyAsync(t->d_kf_backup, t->d_kf, kbytes, hipMemcpyDeviceToDevice, t->stream));
         int rc = trk_launch(t, n_epochs, nullptr);  // warm-up
         if (rc != GSH_OK) return rc;
         float total = 0.0f;
@@ -3204,6 +3393,7 @@ extern "C"
             {
                 GSH_HIP(hipMemcpyAsync(t->d_chan, t->d_chan_backup, bytes, hipMemcpyDeviceToDevice, t->stream));
                 GSH_HIP(hipMemcpyAsync(t->d_lock, t->d_lock_backup, lbytes, hipMemcpyDeviceToDevice, t->stream));
+                if (kbytes) GSH_HIP(hipMemcpyAsync(t->d_kf, t->d_kf_backup, kbytes, hipMemcpyDeviceToDevice, t->stream));
                 GSH_HIP(hipEventRecord(t->ev0, t->stream));
                 rc = trk_launch(t, n_epochs, nullptr);
                 if (rc != GSH_OK) return rc;
@@ -3215,6 +3405,7 @@ extern "C"
             }
         GSH_HIP(hipMemcpyAsync(t->d_chan, t->d_chan_backup, bytes, hipMemcpyDeviceToDevice, t->stream));
         GSH_HIP(hipMemcpyAsync(t->d_lock, t->d_lock_backup, lbytes, hipMemcpyDeviceToDevice, t->stream));
+        if (kbytes) GSH_HIP(hipMemcpyAsync(t->d_kf, t->d_kf_backup, kbytes, hipMemcpyDeviceToDevice, t->stream));
         GSH_HIP(hipStreamSynchronize(t->stream));
         *avg_ms = total / static_cast<float>(reps);
         return coop_check(t);

@@ -11,11 +11,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import TrkConf, TrkEpoch, check, fptr
+from ._lib import TrkConf, TrkEpoch, TrkKfConf, check, fptr
 
 
 def trk_conf(**kw) -> TrkConf:
-    """gsh_trk_conf with Dll_Pll_Conf's defaults (src/algorithms/tracking/libs/dll_pll_conf.h:33-90)."""
+    """gsh_trk_conf with Dll_Pll_Conf's defaults (src/algorithms/tracking/libs/dll_pll_conf.h:33-90).
+
+    The Kalman block's own configuration (Kf_Conf, libs/kf_conf.cc:49, 110) differs in two of them: early_late_space_chips 0.25 and
+    bit_synchronization_time_limit_s = pull_in_time_s + 60; a caller that models GPS_L1_CA_KF_Tracking passes them (see kf_conf, TrackingLoop.set_kalman)."""
     c = TrkConf()
     d = dict(fs_in=4e6, code_chip_rate=1.023e6, signal_carrier_freq=1575.42e6, cfo_frequency_hz=0.0, code_length_chips=1023,
              code_samples_per_chip=1, vector_length=4000, veml=0, track_pilot=0, early_late_space_chips=0.5,
@@ -42,6 +45,18 @@ def trk_conf(**kw) -> TrkConf:
     for k, v in d.items():
         setattr(c, k, v)
     return c
+
+
+def kf_conf(**kw) -> TrkKfConf:
+    """gsh_trk_kf_conf with Kf_Conf's defaults (src/algorithms/tracking/libs/kf_conf.cc:39-48)."""
+    k = TrkKfConf()
+    d = dict(code_disc_sd_chips=0.2, carrier_disc_sd_rads=0.3, code_phase_sd_chips=0.15, carrier_phase_sd_rad=0.25, carrier_freq_sd_hz=0.6,
+             carrier_freq_rate_sd_hz_s=0.01, init_code_phase_sd_chips=0.5, init_carrier_phase_sd_rad=0.7, init_carrier_freq_sd_hz=5.0,
+             init_carrier_freq_rate_sd_hz_s=1.0)
+    d.update(kw)
+    for name, v in d.items():
+        setattr(k, name, v)
+    return k
 
 
 class TrackingLoop:
@@ -131,6 +146,17 @@ class TrackingLoop:
     def set_split(self, work_groups_per_channel: int) -> None:
         """gsh_trk_set_split: work-groups that share every window of a channel in launched runs (1 = off)."""
         check(self._lib.gsh_trk_set_split(self._h, work_groups_per_channel))
+
+    def set_kalman(self, kf: TrkKfConf | None) -> None:
+        """gsh_trk_set_kalman: close the loop with kf_tracking's Kalman filter instead of the DLL/PLL (None: back); only while no channel is started."""
+        check(self._lib.gsh_trk_set_kalman(self._h, C.byref(kf) if kf is not None else None))
+
+    def kf_state(self, channel: int):
+        """-> (x[4], P[4, 4], R[2]) of the channel's filter after the last completed run"""
+        x, P, R = np.zeros(4), np.zeros((4, 4)), np.zeros(2)
+        dp = C.POINTER(C.c_double)
+        check(self._lib.gsh_trk_kf_state(self._h, channel, x.ctypes.data_as(dp), P.ctypes.data_as(dp), R.ctypes.data_as(dp)))
+        return x, P, R
 
     def time_run(self, n_epochs: int, reps: int = 5) -> float:
         ms = C.c_float(0.0)

@@ -629,6 +629,33 @@ extern "C"
     /* HIP-event milliseconds of one gsh_trk_run-sized launch, averaged over reps (each rep restarts from the state at
      * entry; the state is restored afterwards) */
     int gsh_trk_time_run(gsh_trk_t* t, int n_epochs, int reps, float* avg_ms);
+    /* ---- Kalman-filter loop: the reference's second tracking family, kf_tracking (kf.cc = src/algorithms/tracking/gnuradio_blocks/kf_tracking.cc,
+     * Kf_Conf = T/kf_conf.{h,cc}, adapter gps_l1_ca_kf_tracking).  It drives the same correlator and the same state machine as dll_pll_veml_tracking --
+     * pull-in, state 2, secondary-code / bit synchronisation, states 3 and 4, lock detectors, C/N0 -- and differs in run_Kf (kf.cc:1143-1218) in place of
+     * run_dll_pll, in its update_tracking_vars (:1251-1327) and in init_kf / update_kf_narrow_integration_time / update_kf_cn0 (:871-969): a four-state
+     * filter x = [code phase (chips), carrier phase (rad), Doppler (Hz), Doppler rate (Hz/s)] fed with the code and the carrier discriminator
+     * (csrc/kalman_step.h: the arithmetic, FP64, with the order of every sum written out).  gsh_trk_set_kalman switches a handle to that loop (NULL: back
+     * to DLL/PLL); only while no channel is started.  GSH_ERR_INVALID: high_dyn (the smoother that overwrites the Doppler rate, kf.cc:1269-1291, is not
+     * modelled), enable_doppler_correction (kf_tracking has none), a split other than 1, enable_symbol_sync without enable_lock_detectors (state 4 rebuilds
+     * R from the C/N0 estimate, kf.cc:1973), a standard deviation that is negative or not finite.  GSH_ERR_STATE: a channel is active, a run or a live
+     * residency is in flight.  On a Kalman handle gsh_trk_set_split(!= 1) and gsh_trk_live_begin return GSH_ERR_INVALID (launched runs of one work-group per
+     * channel only); start*, run, run_begin / _end, time_run (which saves and restores the filters too), positions, stop and the stream setters work unchanged.
+     * IGNORED in Kalman mode: pll_bw_hz, pll_bw_narrow_hz, dll_bw_hz, dll_bw_narrow_hz, fll_bw_hz, pll_filter_order, dll_filter_order (still range-checked by
+     * gsh_trk_create), enable_fll_pull_in, enable_fll_steady_state, carrier_aiding and cfo_frequency_hz (kf.cc:1265 has no offset term).  Note Kf_Conf's own
+     * defaults: early_late_space_chips 0.25, bit_synchronization_time_limit_s = pull_in_time_s + 60 (kf_conf.cc:49, 110).
+     * gsh_trk_epoch keeps its layout and carries what kf_tracking::log_data logs (kf.cc:1443-1539): carrier_doppler_hz = x[2], code_freq_chips =
+     * d_code_freq_kf_chips_s, carr_phase_error_hz = carrier discriminator / 2 pi, carr_error_filt_hz = x[2], carr_freq_error_hz = x[3] (Doppler rate, Hz/s),
+     * code_error_chips = code discriminator, code_error_filt_chips = d_code_error_kf_chips (all 0 in a state-3 period, as in the DLL/PLL loop); everything
+     * else as there.  The reference's KF dump file (96 bytes per period) differs from the 108-byte DLL/PLL dump gsh_trk_write_dump writes: not provided. */
+    typedef struct gsh_trk_kf_conf            /* Kf_Conf, kf_conf.h:40-55; defaults kf_conf.cc:39-48 */
+    {
+        double code_disc_sd_chips, carrier_disc_sd_rads;                       /* R   (0.2, 0.3) */
+        double code_phase_sd_chips, carrier_phase_sd_rad, carrier_freq_sd_hz, carrier_freq_rate_sd_hz_s;   /* Q   (0.15, 0.25, 0.6, 0.01) */
+        double init_code_phase_sd_chips, init_carrier_phase_sd_rad, init_carrier_freq_sd_hz, init_carrier_freq_rate_sd_hz_s; /* P0  (0.5, 0.7, 5, 1) */
+    } gsh_trk_kf_conf;
+    int gsh_trk_set_kalman(gsh_trk_t* t, const gsh_trk_kf_conf* kf);
+    /* the channel's filter after the last completed run: x[4], P[16] row-major, the diagonal of R (each may be NULL) */
+    int gsh_trk_kf_state(gsh_trk_t* t, int channel, double x[4], double P[16], double R[2]);
     /* write (append != 0: append) the records of one channel as a tracking dump file in the block's own binary layout
      * (log_data, trk.cc:1599-1702: 19 floats, the PRN start sample as uint64 and as double, PRN, TOW [ms] as uint64, week number =
      * 108 bytes per logged period -- the layout save_matfile (trk.cc:1705-1716) and utils/matlab/libs/dll_pll_veml_read_tracking_dump.m
