@@ -30,6 +30,7 @@ constexpr int MC_MARGIN = 32;  // guard entries on each side of the LDS code tab
 // The doubled region is sized for the longest code the flavour takes, so that the plain table's place does not depend on the job.
 constexpr int MC_HALF_MAX_CODE_LEN = 1024;                               // the half-index h = floor(2 w) comes out of a half-precision pattern: h < 2048
 constexpr int MC_HALF_WORDS = 2 * (MC_HALF_MAX_CODE_LEN + 2 * MC_MARGIN);  // 2 176 words = 8 704 bytes
+// (the host builds that LDS content once per code -- multicorrelator.h mcorr_build_half_image -- and the half-chip kernels copy it)
 #ifndef GSH_MC_SCAN_ALL_AT_ONCE
 #define GSH_MC_SCAN_ALL_AT_ONCE 1  // wave sums of the 1 024-thread kernel: one v_add_f32_dpp per value and step (round 4: 7.63 -> 7.50 us per period)
 #endif
@@ -927,15 +928,46 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
     // compute unit) gets by with PF = 1; the closed-loop kernel has ONE work-group per channel and ran PF = 4 until measurement showed PF = 1 to be as fast.
     // (Measured, round 2, profiles/r02/closed_loop_phases.txt: the depth hardly matters -- of the 11 us of a closed-loop period 2.4 us are thread
     // 0's loop arithmetic, 2.6 us fixed cost of the correlation phase (barriers, reductions) and 6 us the 13 trips of each wave.)
-    const float2* const q0 = base + 2 * tid;  // the lane's pair of chunk 0
     constexpr int TRIP = 2 * NCH * PPC;        // samples (float2) a trip advances by
     // the four samples of trip i for this lane: 16-byte loads in the body; at the segment's edges (odd head, partial tail) the samples outside
     // [n_begin, n_end) are read as zero -- never loaded.  Edge trips go through the same queue, so their latency is hidden like the others'.
-    const unsigned lane_bytes = 16u * static_cast<unsigned>(tid);  // the lane's 16 bytes inside a chunk
+    // the lane's 16 bytes inside a chunk.  ONE register for the whole segment: the plain loads pass it through an empty asm in place (see below), so no copy is made;
+    // the cold blocks (re-seed, edge trips) take a copy of their own
+    unsigned lane_bytes = 16u * static_cast<unsigned>(tid);
+    // A trip's base address is wave-uniform and is formed in SGPRs; the lane adds its constant 32-bit byte offset in the load itself (global_load ... v, s[..]).  The empty asm
+    // pins the base to a scalar register pair: left to itself the compiler re-associates base + lane + trip into a per-lane 64-bit pointer (two VGPRs) and one
+    // v_lshl_add_u64 per trip (ISA, round 7).
+    // (the pinned pointer keeps its address space by its type -- what comes out of an asm is otherwise a generic pointer, flat_load -- and the samples are read as
+    //  a plain vector of four floats: float4 is a class, which has no copy from another address space)
+    typedef const __attribute__((address_space(1))) char* global_bytes;
+    typedef float v4f_t __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) v4f_t* global_v4f;
+    typedef const __attribute__((address_space(1))) v2f* global_v2f;
+    auto trip_base = [&](int i, int byte_off) -> global_bytes {
+        global_bytes ub = (global_bytes)(reinterpret_cast<const char*>(base + static_cast<long long>(i) * TRIP) + byte_off);
+        asm("" : "+s"(ub));
+        return ub;
+    };
+    auto load16 = [](global_bytes p) -> float4 {
+        const v4f_t v = *(global_v4f)p;
+        return make_float4(v.x, v.y, v.z, v.w);
+    };
+    auto load8 = [](global_bytes p) -> float2 {
+        const v2f v = *(global_v2f)p;
+        return make_float2(v.x, v.y);
+    };
+    // the integer sample number of the lane's first sample of trip i.  Only a re-seed or an edge trip reads it: it is formed THERE, from the wave-uniform trip index and the
+    // lane's 2 tid, which the empty asm hides -- otherwise it becomes an induction variable with a v_add_u32 in every trip (ISA, round 7)
+    auto lane_n0 = [&](int i) -> int {
+        unsigned lb = lane_bytes;
+        asm volatile("" : "+v"(lb));
+        return (c.n_first + i * TRIP) + static_cast<int>(lb >> 3);
+    };
     auto load_plain = [&](int i, float4& va, float4& vb) {
             {
-                // a wave-uniform 64-bit base plus a 32-bit lane offset: the loads take their base from SGPRs, and no per-lane pointer is carried (and advanced) in VGPRs
-                const char* const ua = reinterpret_cast<const char*>(base + static_cast<long long>(i) * TRIP);
+                // (the lane offset is widened HERE, next to the loads: widened once in front of the loop it is a 64-bit VGPR pair that instruction selection, block by
+                //  block, no longer recognises as a 32-bit offset, and the address is a v_lshl_add_u64 again)
+                asm volatile("" : "+v"(lane_bytes));
 #ifdef GSH_EXP_NOLOAD  // timing experiment only (profiles/r02/mcorr_bound_experiments.txt): no sample traffic
                 va = make_float4(1.0f, static_cast<float>(i), 0.5f, 0.25f);
                 if (NCH == 2) vb = make_float4(0.5f, static_cast<float>(i), 1.0f, 0.25f);
@@ -946,30 +978,32 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
                     {
                         // chunk A / B at -/+ half a chunk around the middle: both inside the 13-bit immediate offset of global_load (a whole chunk, 16 PPC = 4096
                         // bytes at 256 threads, is one more than the field holds and cost a 64-bit add per trip)
-                        const char* const mid = ua + 8 * PPC + lane_bytes;
-                        va = *reinterpret_cast<const float4*>(mid - 8 * PPC);
-                        vb = *reinterpret_cast<const float4*>(mid + 8 * PPC);
+                        const global_bytes mid = trip_base(i, 8 * PPC) + lane_bytes;
+                        va = load16(mid - 8 * PPC);
+                        vb = load16(mid + 8 * PPC);
                     }
                 else
-                    va = *reinterpret_cast<const float4*>(ua + lane_bytes);
+                    va = load16(trip_base(i, 0) + lane_bytes);
 #endif
             }
     };
     auto load_edge = [&](int i, float4& va, float4& vb) {
-        const float2* q = q0 + static_cast<long long>(i) * TRIP;
             {
-                const int n0 = c.n_first + 2 * tid + i * TRIP;
+                const int n0 = lane_n0(i);
+                unsigned lb = lane_bytes;  // (a copy, in this cold block: widened to 64 bits the offset itself would become half of a register pair, with copies in every trip)
+                asm volatile("" : "+v"(lb));
+                const global_bytes q = trip_base(i, 0) + lb;
                 const int lo = c.n_begin, hi = c.n_end - 1;
                 const bool a0 = (n0 >= lo) && (n0 <= hi), a1 = (n0 + 1 >= lo) && (n0 + 1 <= hi);
-                const float2 x0 = a0 ? q[0] : make_float2(0.0f, 0.0f);
-                const float2 x1 = a1 ? q[1] : make_float2(0.0f, 0.0f);
+                const float2 x0 = a0 ? load8(q) : make_float2(0.0f, 0.0f);
+                const float2 x1 = a1 ? load8(q + 8) : make_float2(0.0f, 0.0f);
                 va = make_float4(x0.x, x0.y, x1.x, x1.y);
                 if (NCH == 2)
                     {
                         const int m0 = n0 + 2 * PPC;
                         const bool b0 = (m0 >= lo) && (m0 <= hi), b1 = (m0 + 1 >= lo) && (m0 + 1 <= hi);
-                        const float2 z0 = b0 ? q[2 * PPC] : make_float2(0.0f, 0.0f);
-                        const float2 z1 = b1 ? q[2 * PPC + 1] : make_float2(0.0f, 0.0f);
+                        const float2 z0 = b0 ? load8(q + 16 * PPC) : make_float2(0.0f, 0.0f);
+                        const float2 z1 = b1 ? load8(q + 16 * PPC + 8) : make_float2(0.0f, 0.0f);
                         vb = make_float4(z0.x, z0.y, z1.x, z1.y);
                     }
             }
@@ -1168,9 +1202,9 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
         constexpr int j = decltype(jc)::value;
         constexpr bool FA = decltype(fa)::value, FB = decltype(fb)::value;
         constexpr bool KP = decltype(kp)::value;  // the caller knows that trip i is a plain one (first_plain <= i < last_plain)
-        const int n0 = (c.n_first + i * TRIP) + 2 * tid;  // (uniform part first: used at re-seeds and edges only)
         if (until_reseed == 0)  // uniform: exact re-seed of the lane's phasor and of (float)n
             {
+                const int n0 = lane_n0(i);
                 if (!single && !fac && r_idx - tbl0 >= TBL)
                     {
                         tbl0 = r_idx;
@@ -1199,6 +1233,7 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
                 // chip index stays within what is staged.  (The empty volatile asm keeps this a BRANCH: if-converted, its 16 clamp /
                 // convert / select instructions ran in every trip -- a fifth of the loop's VALU work, ISA of round 2.)
                 asm volatile("" ::: "memory");
+                const int n0 = lane_n0(i);
                 const int lo = c.n_begin, hi = c.n_end - 1;
                 ia = (v2f){static_cast<float>(min(max(n0, lo), hi)), static_cast<float>(min(max(n0 + 1, lo), hi))};
                 const int m0 = n0 + 2 * PPC;
@@ -1312,7 +1347,7 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
             };
             // (the shape of the loops is the one below -- a run of paired trips, then ONE trip of the other kind -- because that is the shape whose joins the register
             //  allocator gets through without copies: an if / else of the two kinds put two dozen v_mov_b64 and a scratch slot at every end of a run.  A run that
-            //  ends at a mask word's end is followed by one per-tap trip it did not need: one in 32.)
+            //  is used up asks again before it falls into the per-tap trip: paired_run stops at a mask word's end, and the run may go on in the next word.)
             while (i < n_trips)
                 {
                     int run = paired_run(i);
@@ -1321,6 +1356,7 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
                             trip(i, j0{}, yes{}, integral_constant<bool, NCH == 2>{}, no{});
                             i++;
                             run--;
+                            if (run == 0) run = paired_run(i);  // uniform
                         }
                     if (i >= n_trips) break;
                     trip(i, j0{}, no{}, no{}, no{});

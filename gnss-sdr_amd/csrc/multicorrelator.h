@@ -22,6 +22,23 @@ __host__ __device__ inline bool mcorr_half_chip_eligible(int n_taps, const float
     return mcorr_pair_eligible(n_taps, shifts, code_step, mode) && shifts[0] == -0.5f && shifts[2] == 0.5f && code_len <= MCORR_HALF_MAX_CODE_LEN;
 }
 
+// The LDS image of a code as the half-chip flavour stages it (mcorr_device.h packed_trip), built once per gsh_bank_set_code and copied by every work-group:
+// the doubled guard-banded table D[2 i] = D[2 i + 1] = table[i] at word 0 (sized for the longest code the flavour takes), the plain guard-banded table
+// table[i] = code[(i - MARGIN) mod len], i in [0, len + 2 MARGIN), at word MCORR_HALF_WORDS; what lies behind either table is zero.
+constexpr int MCORR_MARGIN = 32;                                                                  // guard entries on each side of a code table
+constexpr int MCORR_HALF_WORDS = 2 * (MCORR_HALF_MAX_CODE_LEN + 2 * MCORR_MARGIN);                // the doubled table's room
+constexpr int MCORR_HALF_IMAGE_WORDS = MCORR_HALF_WORDS + MCORR_HALF_MAX_CODE_LEN + 2 * MCORR_MARGIN;  // 3 264 words, a whole number of 16-byte rows
+static_assert(MCORR_HALF_WORDS % 4 == 0 && MCORR_HALF_IMAGE_WORDS % 4 == 0, "the image is copied in 16-byte rows");
+inline void mcorr_build_half_image(const float* code, int code_len, float* image)
+{
+    for (int i = 0; i < MCORR_HALF_IMAGE_WORDS; i++) image[i] = 0.0f;
+    for (int i = 0; i < code_len + 2 * MCORR_MARGIN; i++)
+        {
+            const int k = ((i - MCORR_MARGIN) % code_len + code_len) % code_len;
+            image[2 * i] = image[2 * i + 1] = image[MCORR_HALF_WORDS + i] = code[k];
+        }
+}
+
 struct McorrArgs
 {
     const float2* stream;            // device, complex64 IF samples
@@ -30,6 +47,7 @@ struct McorrArgs
     const float* codes;              // device, n_slots * code_stride floats
     const int* code_lens;            // device, n_slots
     int code_stride;
+    const float* code_images;        // device, n_slots * MCORR_HALF_IMAGE_WORDS floats (mcorr_build_half_image), or nullptr: no launch of this bank takes the half-chip flavour
     float2* out;                     // device, n_jobs * GSH_MAX_TAPS
     float2* partials;                // device, n_jobs * splits * GSH_MAX_TAPS (splits > 1 only)
     int n_jobs;

@@ -168,27 +168,49 @@ __global__ __launch_bounds__(MC_THREADS, ((NT <= 3 && !AUX) ? GSH_MC_MIN_WAVES :
                 misfit = (c.n_end > c.n_begin);  // cannot happen for a batch the host admitted (bank_window_floats); reported as NaN if it does
             lds_floats = a.window_floats;
         }
+    else if constexpr (HALF)
+        {
+            // both tables are a copy of the image the host built when the code was set (multicorrelator.h mcorr_build_half_image: doubled table, plain table, guard bands
+            // and all, laid out as the LDS is): 16-byte rows, first those the doubled table fills, then those of the plain one.  (Built here, element by element, the two
+            // tables cost every thread 8 loads, 16 LDS stores and their addresses -- in each of a launch's 12 800 work-groups, for a content that changes with the satellite.)
+            // The last row of either table may reach up to three words beyond it: zeros of the image, into the padding in front of MC_HALF_WORDS / of `red`.
+            static_assert(MC_MARGIN == MCORR_MARGIN && MC_HALF_WORDS == MCORR_HALF_WORDS, "the host's image and the kernel's LDS layout");
+            const int tab_len = c.code_len + 2 * MC_MARGIN;
+            const int rows_dbl = (2 * tab_len + 3) >> 2, rows = rows_dbl + ((tab_len + 3) >> 2);
+            // every load goes out before the first store waits for one (a loop of load, wait, store pays the L2 round trip once per row); a thread with fewer rows than
+            // the others copies the last row again -- no branch, the same value to the same place.  A row's byte offset is the same in the image and in the LDS.
+            const char* const image = reinterpret_cast<const char*>(a.code_images + static_cast<size_t>(J.code_slot) * MCORR_HALF_IMAGE_WORDS);
+            constexpr int PER_THREAD = (MCORR_HALF_IMAGE_WORDS / 4 + MC_THREADS - 1) / MC_THREADS;
+            const unsigned last = 16u * static_cast<unsigned>(rows - 1), end_dbl = 16u * static_cast<unsigned>(rows_dbl);
+            const unsigned skip = 4u * MC_HALF_WORDS - end_dbl;  // from the doubled table's last row to the plain table's first
+            unsigned at[PER_THREAD];
+            float4 row[PER_THREAD];
+            typedef float row_t __attribute__((ext_vector_type(4)));
+            typedef __attribute__((address_space(3))) row_t* lds_row_ptr;
+#pragma unroll
+            for (int i = 0; i < PER_THREAD; i++)
+                {
+                    const unsigned r = min(16u * static_cast<unsigned>(tid + i * MC_THREADS), last);
+                    at[i] = r < end_dbl ? r : r + skip;
+                    row[i] = *reinterpret_cast<const float4*>(image + at[i]);
+                }
+#pragma unroll
+            for (int i = 0; i < PER_THREAD; i++)  // (the dynamic LDS starts at address 0, checked above: the byte offset IS the address, one ds_write_b128)
+                *reinterpret_cast<lds_row_ptr>(at[i]) = (row_t){row[i].x, row[i].y, row[i].z, row[i].w};
+            lds_floats = tab_len + MC_HALF_WORDS;
+        }
     else
         {
             // the code itself: straight copies (no wrap arithmetic); then the two guard bands, one element per thread of the first wave
             // (the single loop with a wrap per element cost ~150 VALU instructions per wave -- 7 % of everything a wave executes for a 25 000-sample window)
-            // (HALF: every value goes into the doubled table as well, two equal words in one 8-byte store: lds[2 i] = lds[2 i + 1] = tab[i])
             const int tab_len = c.code_len + 2 * MC_MARGIN;
-            float2* const dbl = reinterpret_cast<float2*>(lds);
-            for (int j = tid; j < c.code_len; j += MC_THREADS)
-                {
-                    const float v = gcode[j];
-                    tab[MC_MARGIN + j] = v;
-                    if (HALF) dbl[MC_MARGIN + j] = make_float2(v, v);
-                }
+            for (int j = tid; j < c.code_len; j += MC_THREADS) tab[MC_MARGIN + j] = gcode[j];
             if (tid < 2 * MC_MARGIN)
                 {
                     const int k = tid < MC_MARGIN ? tid - MC_MARGIN : c.code_len + (tid - MC_MARGIN);  // -MARGIN .. -1, len .. len + MARGIN - 1
-                    const float v = gcode[wrap_margin(k, c.code_len)];
-                    tab[MC_MARGIN + k] = v;
-                    if (HALF) dbl[MC_MARGIN + k] = make_float2(v, v);
+                    tab[MC_MARGIN + k] = gcode[wrap_margin(k, c.code_len)];
                 }
-            lds_floats = (AUX ? a.code_stride + 2 * MC_MARGIN : tab_len) + (HALF ? MC_HALF_WORDS : 0);
+            lds_floats = AUX ? a.code_stride + 2 * MC_MARGIN : tab_len;
         }
     // ---- the fused correlator's code (AUX): a second table behind the first
     if (AUX && aux_job >= 0 && !misfit)
@@ -403,7 +425,7 @@ int launch_nt(const McorrArgs& a, int mode, size_t lds, size_t lds_half, hipStre
                         {
                             if (a.window_floats > 0)
                                 hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, true, true>), grid, block, lds, stream, a);
-                            else if (a.half && lds_half > 0)
+                            else if (a.half && lds_half > 0 && a.code_images != nullptr)
                                 hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, false, true, true>), grid, block, lds_half, stream, a);
                             else
                                 hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, false, true>), grid, block, lds, stream, a);

@@ -15,6 +15,7 @@ struct gsh_bank
     int n_slots{0};
     int max_code_len{0};
     float* d_codes{nullptr};
+    float* d_code_images{nullptr};      // per slot, the LDS image of the half-chip flavour (multicorrelator.h mcorr_build_half_image); banks of codes short enough for it only
     int* d_code_lens{nullptr};
     std::vector<int> h_code_lens;
     float2* d_stream_owned{nullptr};
@@ -356,6 +357,12 @@ extern "C"
         hipError_t e;
         if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
         if ((e = hipMalloc(&b->d_codes, sizeof(float) * static_cast<size_t>(n_code_slots) * max_code_length)) != hipSuccess) return fail(e, "hipMalloc(codes)");
+        if (max_code_length <= gsh::MCORR_HALF_MAX_CODE_LEN)
+            {
+                const size_t image_bytes = sizeof(float) * static_cast<size_t>(n_code_slots) * gsh::MCORR_HALF_IMAGE_WORDS;
+                if ((e = hipMalloc(&b->d_code_images, image_bytes)) != hipSuccess) return fail(e, "hipMalloc(code images)");
+                if ((e = hipMemset(b->d_code_images, 0, image_bytes)) != hipSuccess) return fail(e, "hipMemset");
+            }
         if ((e = hipMalloc(&b->d_code_lens, sizeof(int) * n_code_slots)) != hipSuccess) return fail(e, "hipMalloc(code_lens)");
         if ((e = hipMemset(b->d_code_lens, 0, sizeof(int) * n_code_slots)) != hipSuccess) return fail(e, "hipMemset");
         if ((e = hipEventCreate(&b->ev0)) != hipSuccess) return fail(e, "hipEventCreate");
@@ -370,6 +377,7 @@ extern "C"
         (void)hipSetDevice(b->device);
         if (b->stream) (void)hipStreamSynchronize(b->stream);
         if (b->d_codes) (void)hipFree(b->d_codes);
+        if (b->d_code_images) (void)hipFree(b->d_code_images);
         if (b->d_code_lens) (void)hipFree(b->d_code_lens);
         if (b->d_stream_owned) (void)hipFree(b->d_stream_owned);
         if (b->d_jobs) (void)hipFree(b->d_jobs);
@@ -393,6 +401,13 @@ extern "C"
         GSH_HIP(hipSetDevice(b->device));
         GSH_HIP(hipStreamSynchronize(b->stream));
         GSH_HIP(hipMemcpy(b->d_codes + static_cast<size_t>(slot) * b->max_code_len, code, sizeof(float) * code_length, hipMemcpyHostToDevice));
+        if (b->d_code_images != nullptr)
+            {
+                // the slot's LDS image for the half-chip kernels: a host loop over 3 264 words and one copy of 13 KB
+                float image[gsh::MCORR_HALF_IMAGE_WORDS];
+                gsh::mcorr_build_half_image(code, code_length, image);
+                GSH_HIP(hipMemcpy(b->d_code_images + static_cast<size_t>(slot) * gsh::MCORR_HALF_IMAGE_WORDS, image, sizeof(image), hipMemcpyHostToDevice));
+            }
         GSH_HIP(hipMemcpy(b->d_code_lens + slot, &code_length, sizeof(int), hipMemcpyHostToDevice));
         b->h_code_lens[slot] = code_length;
         return GSH_OK;
@@ -532,6 +547,7 @@ extern "C"
         a.codes = b->d_codes;
         a.code_lens = b->d_code_lens;
         a.code_stride = b->max_code_len;
+        a.code_images = b->d_code_images;
         a.out = b->d_out;
         a.partials = b->d_partials;
         a.n_jobs = b->n_jobs;
