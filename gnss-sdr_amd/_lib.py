@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSH_LIB_PATH") or os.path.join(_HERE, "libgnss_sdr_hip.so")  # override: kernel-tuning experiments only
 
 GSH_MAX_TAPS = 8
+GSH_MAX_WIDE_TAPS = 64
 GSH_OK = 0
 GSH_ITEM_GR_COMPLEX, GSH_ITEM_SHORT, GSH_ITEM_BYTE = 0, 1, 2
 ERR_NAMES = {1: "GSH_ERR_INVALID", 2: "GSH_ERR_NO_DEVICE", 3: "GSH_ERR_HIP", 4: "GSH_ERR_STATE", 5: "GSH_ERR_UNSUPPORTED"}
@@ -38,6 +39,22 @@ class CorrJob(C.Structure):
         ("n_taps", C.c_int32),
         ("high_dyn", C.c_int32),
         ("shifts_chips", C.c_float * GSH_MAX_TAPS),
+    ]
+
+
+class CorrJobWide(C.Structure):
+    """gsh_corr_job_wide (296 bytes): up to GSH_MAX_WIDE_TAPS taps, standard resampler and rotator."""
+    _fields_ = [
+        ("sample_offset", C.c_uint64),
+        ("n_samples", C.c_int32),
+        ("code_slot", C.c_int32),
+        ("rem_carr_phase_rad", C.c_float),
+        ("phase_step_rad", C.c_float),
+        ("rem_code_phase_chips", C.c_float),
+        ("code_phase_step_chips", C.c_float),
+        ("n_taps", C.c_int32),
+        ("reserved", C.c_int32),
+        ("shifts_chips", C.c_float * GSH_MAX_WIDE_TAPS),
     ]
 
 
@@ -205,6 +222,8 @@ SYMBOLS = {
     "gsh_bank_set_splits": (C.c_int, [_P, C.c_int]),
     "gsh_bank_set_sample_base": (C.c_int, [_P, C.c_uint64]),
     "gsh_bank_set_stream_ring": (C.c_int, [_P, _P]),
+    "gsh_bank_correlate_wide": (C.c_int, [_P, C.POINTER(CorrJobWide), C.c_int, _F]),
+    "gsh_bank_time_launches_wide": (C.c_int, [_P, C.POINTER(CorrJobWide), C.c_int, C.c_int, _F]),
     "gsh_stream_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(_P)]),
     "gsh_stream_destroy": (None, [_P]),
     "gsh_stream_push": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),

@@ -2,10 +2,12 @@
 // (gsh_bank_*) and the one-to-one Cpu_Multicorrelator_Real_Codes replacement (gsh_mcorr_*)
 // built on top of it.  Host-side bookkeeping only; the arithmetic is in multicorrelator.hip.
 #include "multicorrelator.h"
+#include "multicorrelator_wide.h"
 #include "sample_stream.h"
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <string>
 #include <vector>
 
 struct gsh_bank
@@ -62,6 +64,14 @@ struct gsh_bank
     gsh_corr_job* h_jobs{nullptr};      // pinned staging (ring translation; one-synchronisation gsh_bank_correlate)
     float2* h_out{nullptr};             // pinned
     int h_cap{0};
+    // the wide bank (gsh_bank_correlate_wide, multicorrelator_wide.hip): a job table, outputs and staging of its own -- the narrow calls' staged batch stays as it is
+    gsh_corr_job_wide* d_wjobs{nullptr};
+    float2* d_wout{nullptr};
+    float2* d_wpartials{nullptr};
+    size_t wpartials_cap{0};
+    int wjobs_cap{0};
+    gsh_corr_job_wide* h_wjobs{nullptr};  // pinned
+    float2* h_wout{nullptr};              // pinned
 };
 
 namespace
@@ -330,6 +340,165 @@ int validate_job(const gsh_bank* b, const gsh_corr_job& j, int idx)
         }
     return GSH_OK;
 }
+
+// ---- the wide bank: validation, staging and launch of a batch of gsh_corr_job_wide (the kernels: multicorrelator_wide.hip)
+int validate_job_wide(const gsh_bank* b, const gsh_corr_job_wide& j, int idx)
+{
+    if (j.n_taps < 1 || j.n_taps > GSH_MAX_WIDE_TAPS) return set_error(GSH_ERR_INVALID, "job %d: n_taps %d outside 1..%d", idx, j.n_taps, GSH_MAX_WIDE_TAPS);
+    if (j.n_samples < 1 || j.n_samples > (1 << 30)) return set_error(GSH_ERR_INVALID, "job %d: n_samples %d", idx, j.n_samples);
+    if (j.code_slot < 0 || j.code_slot >= b->n_slots || b->h_code_lens[j.code_slot] <= 0)
+        return set_error(GSH_ERR_STATE, "job %d: code slot %d has no local code", idx, j.code_slot);
+    if (!std::isfinite(j.rem_carr_phase_rad) || !std::isfinite(j.phase_step_rad) || !std::isfinite(j.rem_code_phase_chips) || !std::isfinite(j.code_phase_step_chips))
+        return set_error(GSH_ERR_INVALID, "job %d: a carrier or code parameter is not finite", idx);
+    for (int t = 0; t < j.n_taps; t++)
+        {
+            if (!std::isfinite(j.shifts_chips[t])) return set_error(GSH_ERR_INVALID, "job %d: shift %d is not finite", idx, t);
+            if (t > 0 && j.shifts_chips[t] < j.shifts_chips[t - 1])
+                return set_error(GSH_ERR_INVALID, "job %d: shifts must ascend (shift %d = %g after %g)", idx, t, static_cast<double>(j.shifts_chips[t]),
+                    static_cast<double>(j.shifts_chips[t - 1]));
+        }
+    return GSH_OK;
+}
+
+// an upper bound of the code-table entries one work-group of job j stages: the chip indices of one segment under the widest tap block.  In exact arithmetic
+// hi - lo + 1 <= |step| (seg - 1) + (block's shift span) + 2; each of the chain's three roundings moves either end by at most half an ulp of a value no larger
+// than `mag`.  (The kernel sizes its table from the indices themselves and reports NaN if this were ever short.)
+double wide_table_need(const gsh_corr_job_wide& j, int splits)
+{
+    int seg = (j.n_samples + splits - 1) / splits;
+    seg = (seg + 1) & ~1;
+    const double step = std::fabs(static_cast<double>(j.code_phase_step_chips));
+    double span = 0.0;
+    for (int t0 = 0; t0 < j.n_taps; t0 += gsh::MCORR_WIDE_MAX_BLOCK)
+        {
+            const int t1 = std::min(j.n_taps, t0 + gsh::MCORR_WIDE_MAX_BLOCK) - 1;
+            span = std::max(span, static_cast<double>(j.shifts_chips[t1]) - static_cast<double>(j.shifts_chips[t0]));
+        }
+    const double mag = step * static_cast<double>(j.n_samples) + std::max(std::fabs(static_cast<double>(j.shifts_chips[0])), std::fabs(static_cast<double>(j.shifts_chips[j.n_taps - 1])))
+                       + std::fabs(static_cast<double>(j.rem_code_phase_chips));
+    return step * static_cast<double>(seg) + span + 8.0 + mag * (1.0 / 1048576.0);
+}
+
+// what one wide batch needs besides its job table
+struct WidePlan
+{
+    int max_taps{0};
+    int max_splits{1};
+    int table_floats{1};
+    unsigned long long min_start{~0ull}, max_end{0};  // absolute sample range (sample base applied)
+};
+
+// validate the batch, stage it in pinned memory with every window turned into a position in the attached stream (sample base applied; ring-bound banks:
+// the ring position of the absolute index -- windows never wrap, the ring mirrors its head) and queue the host-to-device copy.  No synchronisation.
+int bank_stage_wide(gsh_bank* b, const gsh_corr_job_wide* jobs, int n_jobs, WidePlan* plan)
+{
+    if (b->d_stream == nullptr) return set_error(GSH_ERR_STATE, "no sample stream attached (gsh_bank_set_stream_*)");
+    const int cap = gsh::mcorr_wide_table_cap();
+    double need_max = 1.0;
+    bool whole_code = false;
+    for (int i = 0; i < n_jobs; i++)
+        {
+            int rc = validate_job_wide(b, jobs[i], i);
+            if (rc != GSH_OK) return rc;
+            const unsigned long long start = static_cast<unsigned long long>(jobs[i].sample_offset) + b->sample_base;
+            const unsigned long long end = start + static_cast<unsigned long long>(jobs[i].n_samples);
+            if (start < b->sample_base || end < start) return set_error(GSH_ERR_INVALID, "job %d: sample_offset %llu", i, static_cast<unsigned long long>(jobs[i].sample_offset));
+            if (b->ring == nullptr && end > b->stream_len)
+                return set_error(GSH_ERR_INVALID, "job %d: the window ends at sample %llu (sample_base %llu), past the %llu-sample stream", i, end, b->sample_base, b->stream_len);
+            plan->min_start = std::min(plan->min_start, start);
+            plan->max_end = std::max(plan->max_end, end);
+            plan->max_taps = std::max(plan->max_taps, jobs[i].n_taps);
+            const int splits = gsh::mcorr_wide_splits(jobs[i].n_samples, b->splits_user);
+            plan->max_splits = std::max(plan->max_splits, splits);
+            const double need = wide_table_need(jobs[i], splits);
+            if (need <= static_cast<double>(cap))
+                need_max = std::max(need_max, need);
+            else
+                whole_code = true;  // this job's tap blocks take the whole code and wrap every index
+        }
+    plan->table_floats = (static_cast<int>(std::ceil(need_max)) + 3) & ~3;
+    if (whole_code) plan->table_floats = std::max(plan->table_floats, (b->max_code_len + 3) & ~3);
+    plan->table_floats = std::min(plan->table_floats, cap);
+    GSH_REQUIRE(!whole_code || b->max_code_len <= cap, "a code of %d samples does not fit the wide bank's table (%d)", b->max_code_len, cap);
+    GSH_HIP(hipSetDevice(b->device));
+    if (n_jobs > b->wjobs_cap)
+        {
+            if (b->d_wjobs) GSH_HIP(hipFree(b->d_wjobs));
+            if (b->d_wout) GSH_HIP(hipFree(b->d_wout));
+            if (b->h_wjobs) GSH_HIP(hipHostFree(b->h_wjobs));
+            if (b->h_wout) GSH_HIP(hipHostFree(b->h_wout));
+            b->d_wjobs = nullptr;
+            b->d_wout = nullptr;
+            b->h_wjobs = nullptr;
+            b->h_wout = nullptr;
+            b->wjobs_cap = 0;
+            const size_t n = static_cast<size_t>(std::max(n_jobs, 32));
+            GSH_HIP(hipMalloc(&b->d_wjobs, sizeof(gsh_corr_job_wide) * n));
+            GSH_HIP(hipMalloc(&b->d_wout, sizeof(float2) * GSH_MAX_WIDE_TAPS * n));
+            GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_wjobs), sizeof(gsh_corr_job_wide) * n, hipHostMallocDefault));
+            GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_wout), sizeof(float2) * GSH_MAX_WIDE_TAPS * n, hipHostMallocDefault));
+            b->wjobs_cap = static_cast<int>(n);
+        }
+    if (plan->max_splits > 1)
+        {
+            const size_t need = static_cast<size_t>(n_jobs) * plan->max_splits * GSH_MAX_WIDE_TAPS;
+            if (need > b->wpartials_cap)
+                {
+                    if (b->d_wpartials) GSH_HIP(hipFree(b->d_wpartials));
+                    b->d_wpartials = nullptr;
+                    b->wpartials_cap = 0;
+                    GSH_HIP(hipMalloc(&b->d_wpartials, sizeof(float2) * need));
+                    b->wpartials_cap = need;
+                }
+        }
+    std::memcpy(b->h_wjobs, jobs, sizeof(gsh_corr_job_wide) * static_cast<size_t>(n_jobs));
+    for (int i = 0; i < n_jobs; i++)
+        {
+            const unsigned long long start = static_cast<unsigned long long>(jobs[i].sample_offset) + b->sample_base;
+            if (b->ring != nullptr)
+                {
+                    const float2* w = nullptr;
+                    int rc = gsh::stream_window(b->ring, start, static_cast<unsigned long long>(jobs[i].n_samples), &w);
+                    if (rc != GSH_OK)
+                        {
+                            const std::string why = gsh_last_error();
+                            return set_error(rc, "job %d: %s", i, why.c_str());
+                        }
+                    b->h_wjobs[i].sample_offset = static_cast<uint64_t>(w - b->ring->d_ring);
+                }
+            else
+                b->h_wjobs[i].sample_offset = start;
+        }
+    if (b->ring != nullptr) b->d_stream = b->ring->d_ring;
+    GSH_HIP(hipMemcpyAsync(b->d_wjobs, b->h_wjobs, sizeof(gsh_corr_job_wide) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
+    return GSH_OK;
+}
+
+int bank_launch_wide(gsh_bank* b, int n_jobs, const WidePlan& plan)
+{
+    gsh::McorrWideArgs a{};
+    a.stream = b->d_stream;
+    a.jobs = b->d_wjobs;
+    a.codes = b->d_codes;
+    a.code_lens = b->d_code_lens;
+    a.code_stride = b->max_code_len;
+    a.out = b->d_wout;
+    a.partials = b->d_wpartials;
+    a.n_jobs = n_jobs;
+    a.splits_user = b->splits_user;
+    a.max_splits = plan.max_splits;
+    a.table_floats = plan.table_floats;
+    a.max_taps = plan.max_taps;
+    if (b->ring != nullptr)
+        {
+            int rc = gsh::stream_wait_pushed(b->ring, plan.max_end, b->stream);  // the push that completed this batch's newest window
+            if (rc != GSH_OK) return rc;
+        }
+    int rc = gsh::mcorr_wide_launch(a, b->stream);
+    if (rc != GSH_OK) return rc;
+    if (b->ring != nullptr) return gsh::stream_mark_read(b->ring, plan.min_start, b->stream);  // pushes that would overwrite these windows wait
+    return GSH_OK;
+}
 }  // namespace
 
 extern "C"
@@ -389,6 +558,11 @@ extern "C"
         if (b->ev1) (void)hipEventDestroy(b->ev1);
         if (b->h_jobs) (void)hipHostFree(b->h_jobs);
         if (b->h_out) (void)hipHostFree(b->h_out);
+        if (b->d_wjobs) (void)hipFree(b->d_wjobs);
+        if (b->d_wout) (void)hipFree(b->d_wout);
+        if (b->d_wpartials) (void)hipFree(b->d_wpartials);
+        if (b->h_wjobs) (void)hipHostFree(b->h_wjobs);
+        if (b->h_wout) (void)hipHostFree(b->h_wout);
         if (b->stream) (void)hipStreamDestroy(b->stream);
         delete b;
     }
@@ -647,6 +821,54 @@ extern "C"
         *avg_ms = ms / static_cast<float>(reps);
         return GSH_OK;
     }
+
+    int gsh_bank_correlate_wide(gsh_bank_t* b, const gsh_corr_job_wide* jobs, int n_jobs, float* out_iq)
+    {
+        // one synchronisation per batch, as gsh_bank_correlate: pinned job table -> H2D -> kernel(s) -> D2H into pinned memory, all queued on the bank's stream
+        GSH_REQUIRE(b != nullptr, "null bank");
+        GSH_REQUIRE(n_jobs >= 0, "n_jobs %d", n_jobs);
+        GSH_REQUIRE(n_jobs == 0 || (jobs != nullptr && out_iq != nullptr), "null argument");
+        if (n_jobs == 0) return GSH_OK;
+        WidePlan plan;
+        int rc = bank_stage_wide(b, jobs, n_jobs, &plan);
+        if (rc == GSH_OK) rc = bank_launch_wide(b, n_jobs, plan);
+        if (rc != GSH_OK)
+            {
+                (void)hipStreamSynchronize(b->stream);
+                return rc;
+            }
+        const size_t bytes = sizeof(float2) * GSH_MAX_WIDE_TAPS * static_cast<size_t>(n_jobs);
+        GSH_HIP(hipMemcpyAsync(b->h_wout, b->d_wout, bytes, hipMemcpyDeviceToHost, b->stream));
+        GSH_HIP(hipStreamSynchronize(b->stream));
+        std::memcpy(out_iq, b->h_wout, bytes);
+        return GSH_OK;
+    }
+
+    int gsh_bank_time_launches_wide(gsh_bank_t* b, const gsh_corr_job_wide* jobs, int n_jobs, int reps, float* avg_ms)
+    {
+        GSH_REQUIRE(b && avg_ms, "null argument");
+        GSH_REQUIRE(n_jobs >= 1 && jobs != nullptr, "no jobs");
+        GSH_REQUIRE(reps >= 1, "reps %d", reps);
+        WidePlan plan;
+        int rc = bank_stage_wide(b, jobs, n_jobs, &plan);
+        if (rc == GSH_OK) rc = bank_launch_wide(b, n_jobs, plan);  // warm-up
+        if (rc == GSH_OK)
+            {
+                GSH_HIP(hipEventRecord(b->ev0, b->stream));
+                for (int i = 0; i < reps && rc == GSH_OK; i++) rc = bank_launch_wide(b, n_jobs, plan);
+            }
+        if (rc != GSH_OK)
+            {
+                (void)hipStreamSynchronize(b->stream);
+                return rc;
+            }
+        GSH_HIP(hipEventRecord(b->ev1, b->stream));
+        GSH_HIP(hipEventSynchronize(b->ev1));
+        float ms = 0.0f;
+        GSH_HIP(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+        *avg_ms = ms / static_cast<float>(reps);
+        return GSH_OK;
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -670,6 +892,49 @@ struct gsh_mcorr
 
 namespace
 {
+// more than GSH_MAX_TAPS correlators: one job of the wide bank (standard resampler and rotator only)
+int mcorr_run_wide(gsh_mcorr* h, int mode, float rem_carr, float phase_step, float rem_code, float code_step, int n)
+{
+    gsh_bank* b = h->bank;
+    if (mode != 0)
+        {
+            // the reference leaves valid results behind every call; a caller that does not look at the status must not see the previous epoch's
+            std::memset(h->corr_out, 0, sizeof(float2) * static_cast<size_t>(h->n_correlators));
+            return set_error(GSH_ERR_UNSUPPORTED,
+                "%d correlators: more than %d run the wide bank, which has the standard resampler only -- call set_high_dynamics_resampler(false)", h->n_correlators,
+                GSH_MAX_TAPS);
+        }
+    gsh_corr_job_wide j;
+    std::memset(&j, 0, sizeof(j));
+    j.sample_offset = 0;
+    j.n_samples = n;
+    j.code_slot = 0;
+    j.rem_carr_phase_rad = rem_carr;
+    j.phase_step_rad = phase_step;
+    j.rem_code_phase_chips = rem_code;
+    j.code_phase_step_chips = code_step;
+    j.n_taps = h->n_correlators;
+    for (int t = 0; t < h->n_correlators; t++) j.shifts_chips[t] = h->shifts[t];
+
+    std::memcpy(h->h_pinned_in, h->sig_in, sizeof(float2) * static_cast<size_t>(n));
+    GSH_HIP(hipMemcpyAsync(h->d_in, h->h_pinned_in, sizeof(float2) * static_cast<size_t>(n), hipMemcpyHostToDevice, b->stream));
+    b->d_stream = h->d_in;
+    b->stream_len = static_cast<unsigned long long>(n);
+    WidePlan plan;
+    int rc = bank_stage_wide(b, &j, 1, &plan);
+    if (rc == GSH_OK) rc = bank_launch_wide(b, 1, plan);
+    if (rc != GSH_OK)
+        {
+            (void)hipStreamSynchronize(b->stream);
+            std::memset(h->corr_out, 0, sizeof(float2) * static_cast<size_t>(h->n_correlators));
+            return rc;
+        }
+    GSH_HIP(hipMemcpyAsync(h->h_pinned_out, b->d_wout, sizeof(float2) * GSH_MAX_WIDE_TAPS, hipMemcpyDeviceToHost, b->stream));
+    GSH_HIP(hipStreamSynchronize(b->stream));
+    std::memcpy(h->corr_out, h->h_pinned_out, sizeof(float2) * static_cast<size_t>(h->n_correlators));
+    return GSH_OK;
+}
+
 int mcorr_run(gsh_mcorr* h, int mode, float rem_carr, float phase_step, float phase_rate, float rem_code, float code_step, float code_rate, int n)
 {
     GSH_REQUIRE(h != nullptr, "null handle");
@@ -679,6 +944,7 @@ int mcorr_run(gsh_mcorr* h, int mode, float rem_carr, float phase_step, float ph
     GSH_REQUIRE(n >= 1 && n <= h->max_len, "signal_length_samples %d outside 1..%d (init size)", n, h->max_len);
     gsh_bank* b = h->bank;
     GSH_HIP(hipSetDevice(h->device));
+    if (h->n_correlators > GSH_MAX_TAPS) return mcorr_run_wide(h, mode, rem_carr, phase_step, rem_code, code_step, n);
 
     gsh_corr_job j;
     std::memset(&j, 0, sizeof(j));
@@ -759,13 +1025,13 @@ extern "C"
     {
         GSH_REQUIRE(h != nullptr, "null handle");
         GSH_REQUIRE(max_signal_length_samples >= 1, "max_signal_length_samples %d", max_signal_length_samples);
-        GSH_REQUIRE(n_correlators >= 1 && n_correlators <= GSH_MAX_TAPS, "n_correlators %d outside 1..%d", n_correlators, GSH_MAX_TAPS);
+        GSH_REQUIRE(n_correlators >= 1 && n_correlators <= GSH_MAX_WIDE_TAPS, "n_correlators %d outside 1..%d", n_correlators, GSH_MAX_WIDE_TAPS);
         gsh_mcorr_free(h);
         GSH_HIP(hipSetDevice(h->device));
         h->max_len = max_signal_length_samples;
         h->n_correlators = n_correlators;
         GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_pinned_in), sizeof(float2) * static_cast<size_t>(max_signal_length_samples), hipHostMallocDefault));
-        GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_pinned_out), sizeof(float2) * GSH_MAX_TAPS, hipHostMallocDefault));
+        GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_pinned_out), sizeof(float2) * GSH_MAX_WIDE_TAPS, hipHostMallocDefault));
         GSH_HIP(hipMalloc(&h->d_in, sizeof(float2) * (static_cast<size_t>(max_signal_length_samples) + 2)));
         GSH_HIP(hipMemset(h->d_in, 0, sizeof(float2) * (static_cast<size_t>(max_signal_length_samples) + 2)));
         return GSH_OK;

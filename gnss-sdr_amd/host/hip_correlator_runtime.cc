@@ -695,7 +695,10 @@ bool Hip_Multicorrelator_Batched::init(int max_signal_length_samples, int n_corr
         }
     if (n_correlators < 1 || n_correlators > GSH_MAX_TAPS || max_signal_length_samples < 1)
         {
-            d_error = "init: n_correlators outside 1..GSH_MAX_TAPS or empty signal length";
+            // (the rendezvous runtime batches gsh_corr_job records; banks of up to GSH_MAX_WIDE_TAPS correlators exist in the synchronous class only)
+            d_error = "init: n_correlators outside 1.." + std::to_string(GSH_MAX_TAPS) +
+                      " or empty signal length (the batched runtime has no wide bank: Hip_Multicorrelator_Real_Codes takes up to " +
+                      std::to_string(GSH_MAX_WIDE_TAPS) + " correlators with set_high_dynamics_resampler(false))";
             return false;
         }
     if (d_channel < 0) d_channel = d_runtime->register_channel();

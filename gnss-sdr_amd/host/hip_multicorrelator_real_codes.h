@@ -28,6 +28,9 @@ public:
     Hip_Multicorrelator_Real_Codes& operator=(const Hip_Multicorrelator_Real_Codes&) = delete;
 
     void set_high_dynamics_resampler(bool use_high_dynamics_resampler);
+    /*! n_correlators: 1..GSH_MAX_WIDE_TAPS (64).  More than GSH_MAX_TAPS (8) run the wide bank, which has the standard resampler only: call
+     *  set_high_dynamics_resampler(false) first (the object's default is true, as in the reference), or every correlate call fails, zeroes the
+     *  n_correlators outputs and leaves the reason in last_error(). */
     bool init(int max_signal_length_samples, int n_correlators);
     bool set_local_code_and_taps(int code_length_chips, const float* local_code_in, float* shifts_chips);
     bool set_input_output_vectors(std::complex<float>* corr_out, const std::complex<float>* sig_in);

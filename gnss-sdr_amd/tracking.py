@@ -14,11 +14,14 @@ from typing import Iterable, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import GSH_MAX_TAPS, CorrJob, check, fptr
+from ._lib import GSH_MAX_TAPS, GSH_MAX_WIDE_TAPS, CorrJob, CorrJobWide, check, fptr
 
 
 class HipMulticorrelatorRealCodes:
-    """Drop-in for Cpu_Multicorrelator_Real_Codes; every method forwards to one gsh_mcorr_* call."""
+    """Drop-in for Cpu_Multicorrelator_Real_Codes; every method forwards to one gsh_mcorr_* call.
+
+    Up to GSH_MAX_WIDE_TAPS correlators; more than GSH_MAX_TAPS run the wide bank, which has the standard resampler only:
+    call set_high_dynamics_resampler(False) (the object's default is True, as in the reference)."""
 
     def __init__(self, device: int = 0):
         self._lib = _lib.load()
@@ -104,6 +107,27 @@ def make_jobs(rows: Iterable[dict]) -> "C.Array[CorrJob]":
     return arr
 
 
+def make_jobs_wide(rows: Iterable[dict]) -> "C.Array[CorrJobWide]":
+    """Build a gsh_corr_job_wide array from the same dicts make_jobs takes (up to GSH_MAX_WIDE_TAPS shifts; standard mode only)."""
+    rows = list(rows)
+    arr = (CorrJobWide * len(rows))()
+    for j, r in zip(arr, rows):
+        sh = list(r.get("shifts_chips", [0.0]))
+        if int(r.get("high_dyn", 0)) != 0:
+            raise ValueError("the wide bank has the standard resampler only (high_dyn must be 0)")
+        j.sample_offset = int(r.get("sample_offset", 0))
+        j.n_samples = int(r["n_samples"])
+        j.code_slot = int(r.get("code_slot", 0))
+        j.rem_carr_phase_rad = float(r.get("rem_carr_phase_rad", 0.0))
+        j.phase_step_rad = float(r.get("phase_step_rad", 0.0))
+        j.rem_code_phase_chips = float(r.get("rem_code_phase_chips", 0.0))
+        j.code_phase_step_chips = float(r.get("code_phase_step_chips", 0.0))
+        j.n_taps = int(r.get("n_taps", len(sh)))
+        for t, v in enumerate(sh[:GSH_MAX_WIDE_TAPS]):
+            j.shifts_chips[t] = float(v)
+    return arr
+
+
 class CorrelatorBank:
     """gsh_bank_*: many (channel, epoch) jobs per launch over a device-resident IF stream."""
 
@@ -163,6 +187,23 @@ class CorrelatorBank:
         check(self._lib.gsh_bank_correlate(self._h, jobs, n, fptr(out)))
         self.n_jobs = n
         return out
+
+    def correlate_wide(self, jobs) -> np.ndarray:
+        """Synchronous batch of jobs with up to GSH_MAX_WIDE_TAPS taps (standard resampler).  Returns complex64 [n_jobs, GSH_MAX_WIDE_TAPS]."""
+        if not isinstance(jobs, C.Array):
+            jobs = make_jobs_wide(jobs)
+        n = len(jobs)
+        out = np.zeros((n, GSH_MAX_WIDE_TAPS), np.complex64)
+        check(self._lib.gsh_bank_correlate_wide(self._h, jobs, n, fptr(out)))
+        return out
+
+    def time_launches_wide(self, jobs, reps: int) -> float:
+        """Upload the wide jobs once; average kernel milliseconds per launch (HIP events on the bank's stream)."""
+        if not isinstance(jobs, C.Array):
+            jobs = make_jobs_wide(jobs)
+        ms = C.c_float(0.0)
+        check(self._lib.gsh_bank_time_launches_wide(self._h, jobs, len(jobs), reps, C.byref(ms)))
+        return ms.value
 
     def upload_jobs(self, jobs) -> None:
         if not isinstance(jobs, C.Array):

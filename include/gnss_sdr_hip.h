@@ -68,7 +68,10 @@ extern "C"
     int gsh_mcorr_create(int device, gsh_mcorr_t** out);
     void gsh_mcorr_destroy(gsh_mcorr_t* h);
 
-    /* mcorr.cc:36-50  bool init(int max_signal_length_samples, int n_correlators) */
+    /* mcorr.cc:36-50  bool init(int max_signal_length_samples, int n_correlators)
+     * n_correlators: 1..GSH_MAX_WIDE_TAPS.  A handle with more than GSH_MAX_TAPS correlators runs the wide bank (section 2b), which has the
+     * standard resampler only: with the high-dynamics flag set (the object's default, as in the reference) its correlate calls return
+     * GSH_ERR_UNSUPPORTED and zero corr_out -- call set_high_dynamics_resampler(false), as dll_pll_veml_tracking and kf_tracking do. */
     int gsh_mcorr_init(gsh_mcorr_t* h, int max_signal_length_samples, int n_correlators);
     /* mcorr.cc:53-63  bool set_local_code_and_taps(int, const float*, float*) */
     int gsh_mcorr_set_local_code_and_taps(gsh_mcorr_t* h, int code_length_chips, const float* local_code_in, float* shifts_chips);
@@ -147,6 +150,39 @@ extern "C"
      * the start of a block -- serves block after block of a long stream or of a ring (positions are taken modulo the ring's capacity)
      * without being re-staged and re-uploaded every time.  The caller keeps the shifted windows inside the stream / resident in the ring. */
     int gsh_bank_set_sample_base(gsh_bank_t* b, uint64_t sample_base);
+
+    /*
+     * (2b) The wide bank: a sampled correlation function -- up to GSH_MAX_WIDE_TAPS taps per job in one pass over the window (multipath
+     *     estimation, signal-quality monitoring, side-peak monitoring), where gsh_corr_job stops at GSH_MAX_TAPS.  Every tap is one output
+     *     of one reference Carrier_wipeoff_multicorrelator_resampler call in STANDARD mode (the standard resampler and rotator: what
+     *     high_dyn = 0 means in gsh_corr_job); the high-dynamics modes exist for up to GSH_MAX_TAPS taps only.  Chip selection is bit-exact
+     *     per tap for any ascending shifts (duplicates, spans wider than a code period, negative raw indices).  A job's output bits depend
+     *     on the job record, the code, the samples and an explicit gsh_bank_set_splits value -- never on the other jobs of the batch.
+     *     Same bank, same codes, same stream attachment (host, device or ring) and sample base as the narrow calls, whose staged job
+     *     table these calls leave alone.
+     */
+#define GSH_MAX_WIDE_TAPS 64
+    typedef struct gsh_corr_job_wide
+    {
+        uint64_t sample_offset;      /* as in gsh_corr_job (ring-bound banks: an absolute sample index) */
+        int32_t n_samples;
+        int32_t code_slot;
+        float rem_carr_phase_rad;
+        float phase_step_rad;
+        float rem_code_phase_chips;
+        float code_phase_step_chips;
+        int32_t n_taps;              /* 1..GSH_MAX_WIDE_TAPS */
+        int32_t reserved;            /* 0 */
+        float shifts_chips[GSH_MAX_WIDE_TAPS]; /* tap offsets in code samples, ascending (equal neighbours allowed) */
+    } gsh_corr_job_wide;             /* 296 bytes, POD */
+    /* one synchronous batch: upload jobs, launch, download.  out_iq: n_jobs * GSH_MAX_WIDE_TAPS complex64 (job-major, tap-minor; taps >= n_taps
+     * are zero).  Jobs of different tap counts may share a batch; n_jobs == 0 is a no-op.  Every job is validated before anything runs
+     * (GSH_ERR_INVALID / GSH_ERR_STATE with the job's index in gsh_last_error()): an empty code slot, a window past the stream or not resident
+     * in the ring, n_taps outside 1..GSH_MAX_WIDE_TAPS, descending shifts, parameters that are not finite. */
+    int gsh_bank_correlate_wide(gsh_bank_t* b, const gsh_corr_job_wide* jobs, int n_jobs, float* out_iq);
+    /* upload `jobs` once, then HIP-event timing of `reps` back-to-back launches on the bank's stream: average milliseconds per launch
+     * (the wide counterpart of gsh_bank_upload_jobs + gsh_bank_time_launches) */
+    int gsh_bank_time_launches_wide(gsh_bank_t* b, const gsh_corr_job_wide* jobs, int n_jobs, int reps, float* avg_ms);
 
     /*
      * (3) The 16-bit family: gsh_mcorr16_* replaces class Cpu_Multicorrelator_16sc
