@@ -3008,6 +3008,7 @@ extern "C"
         lk.use_hist = (c.enable_symbol_sync && c.use_histogram_bit_sync && !c.has_secondary && c.symbols_per_bit > 1) ? 1 : 0;  // trk.cc:1389
         lk.state = 2;            // pull-in hands over to state 2 (trk.cc:1963)
         lk.cloop = c.cloop;      // d_cloop = true at start_tracking (trk.cc:1072); conf.cloop lets a caller start four-quadrant
+        lk.spc_now = c.spc;      // d_trk_parameters.spc as the constructor leaves it: what update_kf_cn0 reads in a state 4 that no extended integration narrowed (kf.cc:952-969, 1973)
         GSH_HIP(hipMemcpyAsync(t->d_lock + channel, &lk, sizeof(lk), hipMemcpyHostToDevice, t->stream));
         gsh::KfState kfs{};
         if (t->kalman)
