@@ -15,6 +15,8 @@ GSH_MAX_TAPS = 8
 GSH_MAX_WIDE_TAPS = 64
 GSH_OK = 0
 GSH_ITEM_GR_COMPLEX, GSH_ITEM_SHORT, GSH_ITEM_BYTE = 0, 1, 2
+GSH_ARRAY_MAX_ANTENNAS, GSH_ARRAY_MAX_BEAMS = 8, 8
+GSH_ARRAY_PLANAR, GSH_ARRAY_INTERLEAVED = 0, 1
 ERR_NAMES = {1: "GSH_ERR_INVALID", 2: "GSH_ERR_NO_DEVICE", 3: "GSH_ERR_HIP", 4: "GSH_ERR_STATE", 5: "GSH_ERR_UNSUPPORTED"}
 
 
@@ -157,6 +159,16 @@ class PackedFormat(C.Structure):
     ]
 
 
+class ArrayFormat(C.Structure):
+    """gsh_array_format (16 bytes): the item type and layout of an antenna array's streams (array.ArrayFormat builds it)."""
+    _fields_ = [
+        ("n_antennas", C.c_int32),
+        ("item_type", C.c_int32),
+        ("layout", C.c_int32),
+        ("first_is_q", C.c_int32),
+    ]
+
+
 class AcqResult(C.Structure):
     """gsh_acq_result."""
     _fields_ = [
@@ -269,6 +281,16 @@ SYMBOLS = {
                                                             C.POINTER(C.c_uint64)]),
     "gsh_stream_group_push_packed": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     "gsh_stream_group_push_packed_device": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "gsh_beam_create": (C.c_int, [C.c_int, C.POINTER(ArrayFormat), C.c_int, C.POINTER(_P)]),
+    "gsh_beam_destroy": (None, [_P]),
+    "gsh_beam_set_weights": (C.c_int, [_P, _F]),
+    "gsh_beam_get_weights": (C.c_int, [_P, _F]),
+    "gsh_beam_process_device": (C.c_int, [_P, C.POINTER(_P), C.c_uint64, C.c_int, C.POINTER(_P), _P]),
+    "gsh_beam_push": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "gsh_beam_push_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.c_uint64, C.c_int, _P, C.POINTER(C.c_uint64)]),
+    "gsh_beam_covariance": (C.c_int, [_P, C.POINTER(_P), C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
+    "gsh_beam_covariance_device": (C.c_int, [_P, C.POINTER(_P), C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
+    "gsh_beam_time_process": (C.c_int, [_P, C.c_uint64, C.c_int, _F]),
     "gsh_fir_create": (C.c_int, [C.c_int, _F, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
     "gsh_fir_destroy": (None, [_P]),
     "gsh_fir_process_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64), _P]),

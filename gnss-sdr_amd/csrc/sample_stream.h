@@ -103,6 +103,18 @@ int stream_write_device_packed(gsh_stream* s, const void* d_src, const PackedCod
 // has validated rings, bands and n; every ring's reader fences, mirror, push event and live words are kept as by the single-ring call)
 int stream_write_device_packed_multi(gsh_stream* const* rings, const int* channels, int n_rings, const void* d_src, const PackedCode& c, unsigned long long n,
     int conj, hipStream_t st);
+// The frame every one-pass push into several rings shares: `st` waits for each ring's reader fences and earlier pushes, the sample range [0, n) is
+// cut wherever one of the rings reaches its capacity boundary, `write` queues samples [first, first + len) of the block on st into dst[r] (ring r's
+// contiguous positions) for each piece, then every ring's mirror, push event, live words and `next` are kept as by its single-ring push.  The caller
+// has validated the rings (stream_multi_check_rings, _live).  n_rings <= 8.
+using MultiSegmentWriter = int (*)(void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t st);
+int stream_write_device_multi(gsh_stream* const* rings, int n_rings, unsigned long long n, hipStream_t st, MultiSegmentWriter write, void* ctx);
+// the all-or-nothing checks of such a push: GSH_ERR_INVALID for a null ring, rings on different devices, a ring named twice, n above a capacity ...
+int stream_multi_check_rings(gsh_stream* const* rings, int n_rings, unsigned long long n);
+// ... and GSH_ERR_STATE for a live tracking channel whose samples the push would overwrite on any ring
+int stream_multi_check_live(gsh_stream* const* rings, int n_rings, unsigned long long n);
+// the ring's raw staging buffer of the synchronous pushes (d_raw), at least nbytes long; an outgrown one is parked while live readers are registered
+int stream_raw_staging(gsh_stream* s, size_t nbytes);
 // validate a packed format for a ring (complex families only) and the byte count of n samples
 int packed_ring_format(const gsh_packed_format* fmt, unsigned long long n, PackedCode* c, unsigned long long* bytes);
 // the two live words of the ring (allocated, and published for what is resident now, at the first call); nullptr + last error on failure

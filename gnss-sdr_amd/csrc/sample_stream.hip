@@ -254,8 +254,7 @@ int stream_write_device_packed(gsh_stream* s, const void* d_src, const PackedCod
     return GSH_OK;
 }
 
-int stream_write_device_packed_multi(gsh_stream* const* rings, const int* channels, int n_rings, const void* d_src, const PackedCode& c, unsigned long long n,
-    int conj, hipStream_t st)
+int stream_write_device_multi(gsh_stream* const* rings, int n_rings, unsigned long long n, hipStream_t st, MultiSegmentWriter write, void* ctx)
 {
     // `st` carries the whole push.  It waits for what each ring's single-ring push would have waited for -- the launches that still read what is
     // overwritten -- and for that ring's earlier pushes where those were queued on another stream (they write the same memory).
@@ -283,7 +282,7 @@ int stream_write_device_packed_multi(gsh_stream* const* rings, const int* channe
             if (a == b) continue;
             float2* dst[8];
             for (int r = 0; r < n_rings; r++) dst[r] = rings[r]->d_ring + (rings[r]->next + a) % rings[r]->capacity;
-            int rc = unpack_packed_multi(d_src, c, a, b - a, conj, channels, n_rings, dst, st);
+            int rc = write(ctx, a, b - a, dst, st);
             if (rc != GSH_OK) return rc;
         }
     for (int r = 0; r < n_rings; r++)
@@ -307,6 +306,62 @@ int stream_write_device_packed_multi(gsh_stream* const* rings, const int* channe
             // what is queued on the ring's own stream from now on (its next push, gsh_stream_wait, gsh_stream_read) comes behind this push
             if (st != s->stream) GSH_HIP(hipStreamWaitEvent(s->stream, s->pushed, 0));
             s->next += n;
+        }
+    return GSH_OK;
+}
+
+int stream_write_device_packed_multi(gsh_stream* const* rings, const int* channels, int n_rings, const void* d_src, const PackedCode& c, unsigned long long n,
+    int conj, hipStream_t st)
+{
+    struct Fanout
+    {
+        const void* d_src;
+        const PackedCode* c;
+        const int* channels;
+        int n_rings, conj;
+    } f{d_src, &c, channels, n_rings, conj};
+    return stream_write_device_multi(
+        rings, n_rings, n, st,
+        [](void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t s) {
+            const Fanout* f = static_cast<const Fanout*>(ctx);
+            return unpack_packed_multi(f->d_src, *f->c, first, len, f->conj, f->channels, f->n_rings, dst, s);
+        },
+        &f);
+}
+
+int stream_multi_check_rings(gsh_stream* const* rings, int n_rings, unsigned long long n)
+{
+    GSH_REQUIRE(rings != nullptr, "null argument");
+    for (int i = 0; i < n_rings; i++)
+        {
+            GSH_REQUIRE(rings[i] != nullptr, "null stream");
+            GSH_REQUIRE(rings[i]->device == rings[0]->device, "the rings of one push lie on one device (ring %d: device %d, ring 0: device %d)", i, rings[i]->device,
+                rings[0]->device);
+            for (int j = 0; j < i; j++) GSH_REQUIRE(rings[j] != rings[i], "ring %d is named twice", i);
+            GSH_REQUIRE(n <= rings[i]->capacity, "a push of %llu samples exceeds the ring capacity %llu", n, rings[i]->capacity);
+        }
+    return GSH_OK;
+}
+
+int stream_multi_check_live(gsh_stream* const* rings, int n_rings, unsigned long long n)
+{
+    for (int i = 0; i < n_rings; i++)
+        {
+            int rc = check_live_floor(rings[i], n);
+            if (rc != GSH_OK) return rc;
+        }
+    return GSH_OK;
+}
+
+int stream_raw_staging(gsh_stream* s, size_t nbytes)
+{
+    if (nbytes > s->raw_cap)
+        {
+            if (s->d_raw) GSH_HIP(release_buffer(s, s->d_raw, false));
+            s->d_raw = nullptr;
+            s->raw_cap = 0;
+            GSH_HIP(hipMalloc(&s->d_raw, nbytes));
+            s->raw_cap = nbytes;
         }
     return GSH_OK;
 }
@@ -348,20 +403,6 @@ int packed_stage_slot(gsh_stream* s, size_t nbytes, int* out)
     return GSH_OK;
 }
 
-// the raw staging buffer of the synchronous pushes, at least nbytes long
-int raw_staging(gsh_stream* s, size_t nbytes)
-{
-    if (nbytes > s->raw_cap)
-        {
-            if (s->d_raw) GSH_HIP(release_buffer(s, s->d_raw, false));
-            s->d_raw = nullptr;
-            s->raw_cap = 0;
-            GSH_HIP(hipMalloc(&s->d_raw, nbytes));
-            s->raw_cap = nbytes;
-        }
-    return GSH_OK;
-}
-
 // the arguments of a multi-ring packed push, all or nothing: the reduced format (fmt->channel is not consulted), the block's size, the bands as int
 int packed_multi_args(gsh_stream_t* const* rings, const int32_t* channels, int n_rings, const gsh_packed_format* fmt, const void* bytes, unsigned long long n,
     gsh::PackedCode* c, unsigned long long* nbytes, int* ch)
@@ -374,26 +415,15 @@ int packed_multi_args(gsh_stream_t* const* rings, const int32_t* channels, int n
     GSH_REQUIRE(gsh::packed_multiband(*c), "packed family %d carries one band: a multi-ring push takes the multi-band families (GSS6450)", fmt->family);
     GSH_REQUIRE(n_rings >= 1 && n_rings <= c->nch, "%d rings for a stream of %d bands", n_rings, c->nch);
     GSH_REQUIRE(n == 0 || bytes != nullptr, "null items");
+    rc = gsh::stream_multi_check_rings(rings, n_rings, n);
+    if (rc != GSH_OK) return rc;
     for (int i = 0; i < n_rings; i++)
         {
-            GSH_REQUIRE(rings[i] != nullptr, "null stream");
-            GSH_REQUIRE(rings[i]->device == rings[0]->device, "the rings of one push lie on one device (ring %d: device %d, ring 0: device %d)", i, rings[i]->device,
-                rings[0]->device);
             GSH_REQUIRE(channels[i] >= 0 && channels[i] < c->nch, "band %d outside 0..%d", channels[i], c->nch - 1);
-            for (int j = 0; j < i; j++)
-                {
-                    GSH_REQUIRE(rings[j] != rings[i], "ring %d is named twice", i);
-                    GSH_REQUIRE(channels[j] != channels[i], "band %d is named twice", channels[i]);
-                }
-            GSH_REQUIRE(n <= rings[i]->capacity, "a push of %llu samples exceeds the ring capacity %llu", n, rings[i]->capacity);
+            for (int j = 0; j < i; j++) GSH_REQUIRE(channels[j] != channels[i], "band %d is named twice", channels[i]);
             ch[i] = channels[i];
         }
-    for (int i = 0; i < n_rings; i++)
-        {
-            rc = check_live_floor(rings[i], n);
-            if (rc != GSH_OK) return rc;
-        }
-    return GSH_OK;
+    return gsh::stream_multi_check_live(rings, n_rings, n);
 }
 }  // namespace
 
@@ -431,7 +461,10 @@ extern "C"
         }
         const size_t total = static_cast<size_t>(s->capacity + s->max_window + 2);
         if ((e = hipMalloc(&s->d_ring, sizeof(float2) * total)) != hipSuccess) return fail(e, "hipMalloc(ring)");
-        if ((e = hipMemset(s->d_ring, 0, sizeof(float2) * total)) != hipSuccess) return fail(e, "hipMemset(ring)");
+        // on the ring's own stream, and waited for: a hipMemset of device memory may return before it has run, on the null stream, which a non-blocking stream
+        // does not wait for -- the first push could be overtaken by it
+        if ((e = hipMemsetAsync(s->d_ring, 0, sizeof(float2) * total, s->stream)) != hipSuccess) return fail(e, "hipMemset(ring)");
+        if ((e = hipStreamSynchronize(s->stream)) != hipSuccess) return fail(e, "hipMemset(ring)");
         *out = s;
         return GSH_OK;
     }
@@ -812,7 +845,7 @@ extern "C"
         if (n == 0) return GSH_OK;
         gsh_stream* s = rings[0];
         GSH_HIP(hipSetDevice(s->device));
-        rc = raw_staging(s, nbytes);
+        rc = gsh::stream_raw_staging(s, nbytes);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipMemcpyAsync(s->d_raw, bytes, nbytes, hipMemcpyHostToDevice, s->stream));
         rc = gsh::stream_write_device_packed_multi(rings, ch, n_rings, s->d_raw, c, n, inverted_spectrum ? 1 : 0, s->stream);

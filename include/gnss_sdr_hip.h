@@ -464,6 +464,58 @@ extern "C"
         uint64_t* first_index);
     int gsh_stream_group_push_packed_device(gsh_stream_group_t* g, const gsh_packed_format* fmt, const void* device_bytes, uint64_t n_samples,
         int inverted_spectrum, uint64_t* first_index);
+    /* ---- antenna array front end: the spatial filter of Array_Signal_Conditioner (Beamformer_Filter, gnss_block_factory.cc:819-839;
+     * src/algorithms/input_filter/gnuradio_blocks/beamformer.{h,cc}) for up to 8 antennas, several beams at once, each beam straight into its own
+     * ring, and the array covariance the weights are computed from.
+     * Arithmetic (the definition): every item becomes a complex float by the integer -> float cast of the ring pushes, (I, Q) per first_is_q,
+     * conjugated when inverted_spectrum.  Then for beam b (beamformer.cc:53-61): sum = (0, 0); for a = 0 .. A-1 in that order
+     *   p.re = x.re w.re - x.im w.im,  p.im = x.re w.im + x.im w.re,  sum += p
+     * in float32 with one rounding per operation, w = weight [b][a].  The reference block has 8 inputs, one output and weights fixed at (1, 0)
+     * (beamformer.h:52; its "dynamically reloadable weights" have no setter); here the antennas, the beams and the weights are the caller's.
+     * A call uses the weights as they stand when it is made (they travel as kernel arguments): gsh_beam_set_weights between two pushes takes
+     * effect exactly at the push boundary.
+     * `items` / `device_items` hold n_antennas pointers for GSH_ARRAY_PLANAR and one pointer for GSH_ARRAY_INTERLEAVED; device pointers are
+     * aligned to the item (2 / 4 / 8 bytes), 16-byte aligned interleaved frames of whole 16-byte words are read with 16-byte loads. */
+#define GSH_ARRAY_MAX_ANTENNAS 8 /* GNSS_SDR_BEAMFORMER_CHANNELS, beamformer.h:37 */
+#define GSH_ARRAY_MAX_BEAMS 8
+#define GSH_ARRAY_PLANAR 0      /* one buffer per antenna: the block's input_items[a] (beamformer.cc:59; Multichannel_File_Signal_Source) */
+#define GSH_ARRAY_INTERLEAVED 1 /* one buffer of sample-major frames, antenna a of sample k is item k*A + a: the wire layout of
+                                   Custom_UDP_Signal_Source for cbyte / ishort / cfloat (gr_complex_ip_packet_source.cc:395-488) */
+    typedef struct
+    {
+        int32_t n_antennas; /* 1..8 */
+        int32_t item_type;  /* enum gsh_item_type */
+        int32_t layout;     /* GSH_ARRAY_PLANAR / _INTERLEAVED */
+        int32_t first_is_q; /* 0: the first value of a pair is I; 1: it is Q (Custom_UDP's IQ_swap = false, gr_complex_ip_packet_source.cc:406-413) */
+    } gsh_array_format;
+    typedef struct gsh_beam gsh_beam_t;
+    /* GSH_ERR_INVALID (before any device is touched) for a null pointer, n_antennas or n_beams outside 1..8, an unknown item type or layout */
+    int gsh_beam_create(int device, const gsh_array_format* fmt, int n_beams /* 1..8 */, gsh_beam_t** out);
+    void gsh_beam_destroy(gsh_beam_t* b);
+    /* n_beams x n_antennas complex64, row-major; default every weight (1, 0), beamformer.h:52 */
+    int gsh_beam_set_weights(gsh_beam_t* b, const float* w_iq);
+    int gsh_beam_get_weights(const gsh_beam_t* b, float* w_iq);
+    /* n samples of every antenna -> beam r at device_out[r] (n complex64, 8-byte aligned), r < n_beams; asynchronous on hip_stream (NULL: the
+     * handle's own stream, synchronous) */
+    int gsh_beam_process_device(gsh_beam_t* b, const void* const* device_items, uint64_t n, int inverted_spectrum, void* const* device_out, void* hip_stream);
+    /* One push of an array block into n_beams rings: beam r goes to rings[r].  The raw block crosses PCIe once and one pass over it writes every
+     * ring; afterwards ring r holds, bit for bit and index for index, what gsh_stream_push(rings[r], beam_r, n, GSH_ITEM_GR_COMPLEX, 0, ...) of the
+     * host-computed beam would have left (resident range, mirror, push event and history, live words), and gsh_stream_wait / gsh_stream_read work
+     * on every ring of the call.  Rings may differ in capacity, window and next index; they lie on the handle's device.  first_index: n_beams
+     * entries, or NULL.  All or nothing, as gsh_stream_push_packed_multi: GSH_ERR_INVALID for a null pointer, a ring named twice, a ring on
+     * another device, n above a ring's capacity; GSH_ERR_STATE for a live tracking channel whose samples the push would overwrite on any ring;
+     * after a refusal no ring has advanced.  The device form works on hip_stream (NULL: the first ring's own stream, synchronous). */
+    int gsh_beam_push(gsh_beam_t* b, gsh_stream_t* const* rings, const void* const* items, uint64_t n, int inverted_spectrum, uint64_t* first_index);
+    int gsh_beam_push_device(gsh_beam_t* b, gsh_stream_t* const* rings, const void* const* device_items, uint64_t n, int inverted_spectrum, void* hip_stream,
+        uint64_t* first_index);
+    /* r_iq: n_antennas x n_antennas complex128, row-major, R[i][j] = sum_n x_i[n] conj(x_j[n]) -- a sum, the caller divides -- of x as the
+     * beamformer sees it (after first_is_q and inverted_spectrum).  Products (exact: two float32 factors) and sums in FP64; the upper triangle
+     * is computed, the lower is its conjugate.  Per-work-group partials added in a fixed order, no floating-point atomics: the same data give
+     * the same bits on every run.  Synchronous. */
+    int gsh_beam_covariance(gsh_beam_t* b, const void* const* items, uint64_t n, int inverted_spectrum, double* r_iq);
+    int gsh_beam_covariance_device(gsh_beam_t* b, const void* const* device_items, uint64_t n, int inverted_spectrum, double* r_iq);
+    /* average time of one beam pass over a zero-filled block of n samples in the handle's format, HIP events, as the other gsh_*_time_* calls */
+    int gsh_beam_time_process(gsh_beam_t* b, uint64_t n, int reps, float* avg_ms);
     /* Direct (nearest-neighbour) resampler, the arithmetic of direct_resampler_conditioner_cc (src/algorithms/resampler/gnuradio_blocks/
      * direct_resampler_conditioner_cc.cc:39-129; used by the signal conditioner and the acquisition decimator, gnss_flowgraph.cc:1165-1209):
      * 32-bit phase accumulator, a sample is copied on every wrap.  Stateless form: outputs are numbered from the start of the stream,
