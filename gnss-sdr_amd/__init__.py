@@ -12,3 +12,4 @@ The directory name carries a hyphen (it is named after the reference repo), so i
 from . import _lib  # noqa: F401
 from ._lib import GSH_MAX_TAPS, GshError, load  # noqa: F401
 from .build import build_library  # noqa: F401
+from .conditioner import SignalConditioner  # noqa: F401

@@ -169,6 +169,24 @@ class ArrayFormat(C.Structure):
     ]
 
 
+class CondConf(C.Structure):
+    """gsh_cond_conf (96 bytes): the signal conditioner's chain (conditioner.SignalConditioner builds it)."""
+    _fields_ = [
+        ("input", C.c_int32),
+        ("item_type", C.c_int32),
+        ("inverted_spectrum", C.c_int32),
+        ("n_taps", C.c_int32),
+        ("taps", C.POINTER(C.c_float)),
+        ("decimation", C.c_int32),
+        ("reserved", C.c_int32),
+        ("center_freq_hz", C.c_double),
+        ("sampling_freq_hz", C.c_double),
+        ("fs_in", C.c_double),
+        ("fs_out", C.c_double),
+        ("packed", PackedFormat),
+    ]
+
+
 class AcqResult(C.Structure):
     """gsh_acq_result."""
     _fields_ = [
@@ -297,6 +315,15 @@ SYMBOLS = {
     "gsh_fir_create_packed": (C.c_int, [C.c_int, _F, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(PackedFormat), C.POINTER(_P)]),
     "gsh_direct_resample_device": (C.c_int, [C.c_int, _P, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_uint64, _P, C.c_uint64,
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P]),
+    "gsh_cond_create": (C.c_int, [C.c_int, C.POINTER(CondConf), C.POINTER(_P)]),
+    "gsh_cond_destroy": (None, [_P]),
+    "gsh_cond_plan": (C.c_int, [C.POINTER(CondConf), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gsh_cond_bind": (C.c_int, [_P, _P]),
+    "gsh_cond_push": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gsh_cond_push_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gsh_cond_push_pinned_async": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gsh_cond_position": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gsh_cond_time_push": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _F]),
     "gsh_trk_create": (C.c_int, [C.c_int, C.POINTER(TrkConf), C.c_int, C.c_int, C.POINTER(_P)]),
     "gsh_trk_destroy": (None, [_P]),
     "gsh_trk_set_stream_host": (C.c_int, [_P, _F, C.c_uint64]),

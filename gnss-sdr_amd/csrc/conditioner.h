@@ -1,0 +1,64 @@
+// The signal conditioner's one-pass kernels (gsh_cond_*, include/gnss_sdr_hip.h): adapter, FIR and resampler per ring sample.  The kernels live in
+// fir_filter.hip, beside fir_kernel, because they call its device functions (fetch_translated: the loose chain's arithmetic by construction); the
+// handle, its bookkeeping and the C ABI are conditioner.hip.
+#ifndef GSH_CONDITIONER_H
+#define GSH_CONDITIONER_H
+#include "gsh_internal.h"
+#include "packed_unpack.h"
+
+namespace gsh
+{
+// what the block's items are (CondArgs::kind): 0 .. 4 are the input kinds of the FIR handle (fir_filter.hip), 5 and 6 the ring's integer item types
+enum
+{
+    COND_CPX_FLOAT = 0,
+    COND_REAL_FLOAT = 1,
+    COND_REAL_SHORT = 2,
+    COND_REAL_BYTE = 3,
+    COND_PACKED = 4,
+    COND_CPX_SHORT = 5,
+    COND_CPX_BYTE = 6
+};
+enum
+{
+    COND_RS_NONE = 0,
+    COND_RS_DECIMATE = 1,
+    COND_RS_INTERPOLATE = 2
+};
+constexpr int COND_TILE = 1024;      // ring samples per work-group at most
+constexpr int COND_MAX_SPAN = 4096;  // staged inputs per work-group: 32 KiB of LDS as float2, four work-groups and more per compute unit
+
+// One launch: ring samples [out0, out0 + n_out) of the conditioner's output stream into `out`.  Passed by value.
+struct CondArgs
+{
+    const void* in;              // the raw block: n_in samples of `kind`, sample 0 at its first byte
+    const float2* hist;          // the n_taps - 1 samples before the block, converted (and conjugated), untranslated
+    float2* hist_out;            // cond_launch_history: receives the new tail
+    const float* taps;
+    float2* out;
+    unsigned long long in0;      // absolute index of the block's first sample
+    unsigned long long n_in;
+    unsigned long long out0;     // absolute output index of out[0]
+    unsigned long long n_out;    // below 2^32
+    unsigned long long q0, r0;   // the resampler's plan for out0: ResampleArgs of resampler.hip (cond_plan_resampler fills them)
+    double rev_per_sample;       // f_c / f_s
+    unsigned step;
+    int rs_mode;                 // COND_RS_*
+    int n_taps;                  // 0: no filter (the sample itself; `hist`, `taps` unused)
+    int decimation;
+    int kind;
+    int conj;                    // inverted_spectrum: conjugate the decoded sample, before the filter
+    int tile, max_span;          // cond_tile(): ring samples per work-group and the inputs they span at most
+    PackedCode packed;           // kind COND_PACKED
+};
+
+// q0, r0 of a launch whose first output is a.out0 (a.step, a.rs_mode set)
+void cond_plan_resampler(CondArgs* a);
+// a.tile, a.max_span for the handle's filter and ratio: the largest power of two of outputs whose inputs fit COND_MAX_SPAN
+void cond_tile(CondArgs* a);
+// queue the launch on st (a.n_out > 0)
+int cond_launch(const CondArgs& a, hipStream_t st);
+// queue the history update: a.hist_out = the last n_taps - 1 converted samples of (a.hist, the block)
+int cond_launch_history(const CondArgs& a, hipStream_t st);
+}  // namespace gsh
+#endif

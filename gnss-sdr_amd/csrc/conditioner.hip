@@ -1,0 +1,432 @@
+// gsh_cond_*: the signal conditioner (Signal_Conditioner, src/algorithms/conditioner/adapters/signal_conditioner.cc:60-87: DataTypeAdapter ->
+// InputFilter -> Resampler) as one handle and one call per block, one pass over the raw block straight into a sample ring.  See
+// include/gnss_sdr_hip.h for the contract.  This file is the host side: the handle, the integer bookkeeping and the pushes; the kernels are in
+// fir_filter.hip (conditioner.h), the ring's wrap, mirror, fences, push event and live words are kept by stream_write_device_multi.
+//
+// Bookkeeping.  After N input samples the filter has completed M = ceil(N / D) outputs (output m needs inputs up to m D) and the resampler every
+// output j whose filter output m(j) is below M:
+//     decimation     m(j) = ceil(j 2^32 / step) < M   <=>   j <= floor((M - 1) step / 2^32)
+//     interpolation  m(j) = floor((j + 1) step / 2^32) < M   <=>   j + 1 < ceil(M 2^32 / step)
+// -- a function of N alone, so the ring's content does not depend on where the stream is cut.  The first output of a push has m(j) >= M of the
+// stream before it, so it reaches back K - 1 input samples at most: that is the history the handle keeps (an interpolating resampler that takes
+// a filter output twice takes it twice in the same push).
+#include "conditioner.h"
+#include "resample_index.h"
+#include "sample_convert.h"
+#include "sample_stream.h"
+#include <new>
+
+namespace
+{
+using gsh::CondArgs;
+using gsh::set_error;
+
+constexpr int COND_MAX_TAPS = 1024;  // FIR_MAX_TAPS of fir_filter.hip
+constexpr int COND_NSTAGE = 4;       // device staging buffers of the page-locked asynchronous push, in rotation
+
+// a validated gsh_cond_conf, reduced to what the pushes need
+struct CondPlan
+{
+    int kind{0};                // COND_* of conditioner.h
+    gsh::PackedCode packed{};
+    size_t item_bytes{0};       // bytes per input sample (not packed)
+    int conj{0};
+    int n_taps{0}, decimation{1};
+    double rev_per_sample{0.0};
+    unsigned step{0};
+    int rs_mode{gsh::COND_RS_NONE};
+};
+
+int reduce_conf(const gsh_cond_conf* conf, CondPlan* p)
+{
+    GSH_REQUIRE(conf != nullptr, "null configuration");
+    bool real = false;
+    switch (conf->input)
+        {
+        case GSH_COND_INPUT_ITEMS:
+            GSH_REQUIRE(gsh::item_bytes(conf->item_type) != 0, "unknown item type %d", conf->item_type);
+            p->kind = conf->item_type == GSH_ITEM_GR_COMPLEX ? gsh::COND_CPX_FLOAT : conf->item_type == GSH_ITEM_SHORT ? gsh::COND_CPX_SHORT : gsh::COND_CPX_BYTE;
+            p->item_bytes = gsh::item_bytes(conf->item_type);
+            break;
+        case GSH_COND_INPUT_REAL:
+            GSH_REQUIRE(conf->item_type >= 1 && conf->item_type <= 3, "real item kind %d outside 1..3 (float32, int16, int8)", conf->item_type);
+            p->kind = conf->item_type;  // COND_REAL_* are the FIR's input kinds
+            p->item_bytes = conf->item_type == 1 ? 4 : conf->item_type == 2 ? 2 : 1;
+            real = true;
+            break;
+        case GSH_COND_INPUT_PACKED:
+            {
+                int rc = gsh::packed_code(&conf->packed, &p->packed);
+                if (rc != GSH_OK) return rc;
+                p->kind = gsh::COND_PACKED;
+                real = !p->packed.cplx;
+                break;
+            }
+        default:
+            return set_error(GSH_ERR_INVALID, "unknown conditioner input %d", conf->input);
+        }
+    GSH_REQUIRE(!real || conf->n_taps != 0, "real input without a filter: the ring holds complex samples (give the taps of a Freq_Xlating_Fir_Filter / Fir_Filter)");
+    GSH_REQUIRE(!real || !conf->inverted_spectrum, "inverted_spectrum on real input: there is no spectrum to mirror before the filter");
+    p->conj = conf->inverted_spectrum ? 1 : 0;
+    p->n_taps = conf->n_taps;
+    p->decimation = 1;
+    if (conf->n_taps != 0)
+        {
+            GSH_REQUIRE(conf->taps != nullptr, "null taps");
+            GSH_REQUIRE(conf->n_taps >= 1 && conf->n_taps <= COND_MAX_TAPS, "n_taps %d outside 1..%d", conf->n_taps, COND_MAX_TAPS);
+            p->decimation = conf->decimation == 0 ? 1 : conf->decimation;
+            GSH_REQUIRE(p->decimation >= 1 && p->decimation <= 64, "decimation %d outside 1..64", conf->decimation);
+            GSH_REQUIRE(conf->sampling_freq_hz > 0.0, "sampling frequency must be positive");
+            p->rev_per_sample = conf->center_freq_hz / conf->sampling_freq_hz;  // (fir_create)
+        }
+    else
+        GSH_REQUIRE(conf->decimation == 0 || conf->decimation == 1, "decimation %d without a filter", conf->decimation);
+    if (conf->fs_in != 0.0 || conf->fs_out != 0.0)
+        {
+            GSH_REQUIRE(conf->fs_in > 0.0 && conf->fs_out > 0.0, "sample rates must be positive");
+            int decimating = 1;
+            p->step = gsh::phase_step_of(conf->fs_in, conf->fs_out, &decimating);
+            GSH_REQUIRE(p->step != 0u || conf->fs_in == conf->fs_out, "resampling ratio %g too extreme for the 32-bit phase accumulator", conf->fs_out / conf->fs_in);
+            p->rs_mode = p->step == 0u ? gsh::COND_RS_NONE : decimating ? gsh::COND_RS_DECIMATE : gsh::COND_RS_INTERPOLATE;  // (a ratio of one copies)
+        }
+    return GSH_OK;
+}
+
+// ring samples produced once n_in input samples have arrived (see the head of the file)
+unsigned long long outputs_after(const CondPlan& p, unsigned long long n_in)
+{
+    const unsigned long long D = static_cast<unsigned long long>(p.decimation);
+    const unsigned long long M = (n_in + D - 1) / D;
+    if (M == 0 || p.rs_mode == gsh::COND_RS_NONE) return M;
+    if (p.rs_mode == gsh::COND_RS_DECIMATE) return static_cast<unsigned long long>((static_cast<unsigned __int128>(M - 1) * p.step) >> 32) + 1;
+    return static_cast<unsigned long long>(((static_cast<unsigned __int128>(M) << 32) + p.step - 1) / p.step) - 1;
+}
+}  // namespace
+
+struct gsh_cond
+{
+    int device{0};
+    CondPlan plan;
+    CondArgs base{};                 // what every launch of the handle shares (taps, filter, ratio, tile)
+    float* d_taps{nullptr};
+    float2* d_hist[2]{nullptr, nullptr};  // the converted history, double-buffered: a push reads [cur] and leaves the new tail in [cur ^ 1]
+    int cur{0};
+    hipEvent_t hist_ev{nullptr};     // behind the latest push's device work: the next push, on whatever stream, comes after it
+    bool hist_recorded{false};
+    gsh_stream* ring{nullptr};
+    unsigned long long ring_base{0};   // ring index of output 0
+    unsigned long long n_in_total{0}, n_out_total{0};
+    hipStream_t stream{nullptr};     // gsh_cond_time_push
+    hipEvent_t ev0{nullptr}, ev1{nullptr};
+    void* d_raw{nullptr};            // staging of gsh_cond_push
+    size_t raw_cap{0};
+    void* d_stage[COND_NSTAGE]{};    // staging of gsh_cond_push_pinned_async
+    size_t stage_cap[COND_NSTAGE]{};
+    hipEvent_t stage_done[COND_NSTAGE]{};  // the launch that read d_stage[i] has finished
+    int stage_next{0};
+};
+
+namespace
+{
+// bytes of a block of n_in samples; GSH_ERR_INVALID for a partial packed item
+int block_bytes(const gsh_cond* h, unsigned long long n_in, unsigned long long* bytes)
+{
+    if (h->plan.kind == gsh::COND_PACKED) return gsh::packed_size(h->plan.packed, n_in, bytes);
+    *bytes = n_in * h->plan.item_bytes;
+    return GSH_OK;
+}
+
+// the arguments of a push, all or nothing: *count = ring samples it completes
+int check_push(const gsh_cond* h, const void* items, unsigned long long n_in, unsigned long long* bytes, unsigned long long* count)
+{
+    GSH_REQUIRE(h != nullptr, "null conditioner");
+    GSH_REQUIRE(n_in == 0 || items != nullptr, "null items");
+    GSH_REQUIRE(h->ring != nullptr, "no ring bound (gsh_cond_bind)");
+    int rc = block_bytes(h, n_in, bytes);
+    if (rc != GSH_OK) return rc;
+    *count = outputs_after(h->plan, h->n_in_total + n_in) - h->n_out_total;
+    gsh_stream* ring = h->ring;
+    rc = gsh::stream_multi_check_rings(&ring, 1, *count);
+    if (rc != GSH_OK) return rc;
+    GSH_REQUIRE(*count < (1ull << 32), "more than 2^32 outputs in one push");  // (the launch's index arithmetic, as gsh_direct_resample_device)
+    if (ring->next != h->ring_base + h->n_out_total)
+        return set_error(GSH_ERR_STATE, "the ring's next index is %llu, the conditioner left it at %llu: someone else pushed or sought", ring->next,
+            h->ring_base + h->n_out_total);
+    return gsh::stream_multi_check_live(&ring, 1, *count);
+}
+
+// the launch arguments of a block at d_block from the handle's present state
+CondArgs block_args(const gsh_cond* h, const void* d_block, unsigned long long n_in)
+{
+    CondArgs a = h->base;
+    a.in = d_block;
+    a.hist = h->d_hist[h->cur];
+    a.hist_out = h->d_hist[h->cur ^ 1];
+    a.in0 = h->n_in_total;
+    a.n_in = n_in;
+    return a;
+}
+
+struct SegmentCtx
+{
+    CondArgs a;                      // of the whole push
+    unsigned long long out0;         // absolute output index of the push's first ring sample
+};
+
+// MultiSegmentWriter: ring samples [first, first + len) of the push into dst[0]
+int write_segment(void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t st)
+{
+    const SegmentCtx* c = static_cast<const SegmentCtx*>(ctx);
+    CondArgs a = c->a;
+    a.out = dst[0];
+    a.out0 = c->out0 + first;
+    a.n_out = len;
+    gsh::cond_plan_resampler(&a);
+    return gsh::cond_launch(a, st);
+}
+
+// queue the device work of a checked push on st and advance the handle
+int push_block(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st)
+{
+    if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
+    SegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total};
+    if (count > 0)
+        {
+            int rc = gsh::stream_write_device_multi(&h->ring, 1, count, st, write_segment, &ctx);
+            if (rc != GSH_OK) return rc;
+        }
+    if (n_in > 0)
+        {
+            if (h->plan.n_taps > 1)
+                {
+                    int rc = gsh::cond_launch_history(ctx.a, st);
+                    if (rc != GSH_OK) return rc;
+                    h->cur ^= 1;
+                }
+            GSH_HIP(hipEventRecord(h->hist_ev, st));
+            h->hist_recorded = true;
+        }
+    h->n_in_total += n_in;
+    h->n_out_total += count;
+    return GSH_OK;
+}
+
+int grow(void** buf, size_t* cap, size_t bytes)
+{
+    if (bytes <= *cap) return GSH_OK;
+    if (*buf) GSH_HIP(hipFree(*buf));  // (hipFree waits for the device: nothing still reads the old buffer)
+    *buf = nullptr;
+    *cap = 0;
+    GSH_HIP(hipMalloc(buf, bytes + bytes / 2));
+    *cap = bytes + bytes / 2;
+    return GSH_OK;
+}
+
+void report(const gsh_cond* h, unsigned long long count, uint64_t* first_out, uint64_t* n_out)
+{
+    if (first_out) *first_out = h->ring_base + h->n_out_total;
+    if (n_out) *n_out = count;
+}
+}  // namespace
+
+extern "C"
+{
+    int gsh_cond_plan(const gsh_cond_conf* conf, uint64_t n_in_total, uint64_t* n_out_total)
+    {
+        GSH_REQUIRE(n_out_total != nullptr, "null n_out_total");
+        *n_out_total = 0;
+        CondPlan p;
+        int rc = reduce_conf(conf, &p);
+        if (rc != GSH_OK) return rc;
+        *n_out_total = outputs_after(p, n_in_total);
+        return GSH_OK;
+    }
+
+    int gsh_cond_create(int device, const gsh_cond_conf* conf, gsh_cond_t** out)
+    {
+        GSH_REQUIRE(out != nullptr, "null out pointer");
+        *out = nullptr;
+        CondPlan p;
+        int rc = reduce_conf(conf, &p);
+        if (rc != GSH_OK) return rc;
+        rc = gsh::use_device(device);
+        if (rc != GSH_OK) return rc;
+        gsh_cond* h = new (std::nothrow) gsh_cond();
+        GSH_REQUIRE(h != nullptr, "out of host memory");
+        h->device = device;
+        h->plan = p;
+        auto fail = [&](hipError_t e, const char* what) {
+            gsh::hip_fail(e, what, __FILE__, __LINE__);
+            gsh_cond_destroy(h);
+            return GSH_ERR_HIP;
+        };
+        hipError_t e;
+        if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
+        if ((e = hipEventCreate(&h->ev0)) != hipSuccess) return fail(e, "hipEventCreate");
+        if ((e = hipEventCreate(&h->ev1)) != hipSuccess) return fail(e, "hipEventCreate");
+        if ((e = hipEventCreateWithFlags(&h->hist_ev, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
+        if (p.n_taps > 0)
+            {
+                if ((e = hipMalloc(&h->d_taps, sizeof(float) * p.n_taps)) != hipSuccess) return fail(e, "hipMalloc(taps)");
+                if ((e = hipMemcpy(h->d_taps, conf->taps, sizeof(float) * p.n_taps, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy(taps)");
+                // a fresh stream has zero history (a fresh GNU Radio buffer, fir_filter.hip)
+                if ((e = hipMalloc(&h->d_hist[0], sizeof(float2) * 2 * static_cast<size_t>(p.n_taps))) != hipSuccess) return fail(e, "hipMalloc(hist)");
+                if ((e = hipMemset(h->d_hist[0], 0, sizeof(float2) * 2 * static_cast<size_t>(p.n_taps))) != hipSuccess) return fail(e, "hipMemset(hist)");
+                h->d_hist[1] = h->d_hist[0] + p.n_taps;
+            }
+        CondArgs& a = h->base;
+        a.taps = h->d_taps;
+        a.rev_per_sample = p.rev_per_sample;
+        a.step = p.step;
+        a.rs_mode = p.rs_mode;
+        a.n_taps = p.n_taps;
+        a.decimation = p.decimation;
+        a.kind = p.kind;
+        a.conj = p.conj;
+        a.packed = p.packed;
+        gsh::cond_tile(&a);
+        *out = h;
+        return GSH_OK;
+    }
+
+    void gsh_cond_destroy(gsh_cond_t* h)
+    {
+        if (!h) return;
+        (void)hipSetDevice(h->device);
+        if (h->hist_recorded) (void)hipEventSynchronize(h->hist_ev);  // the latest push's device work, on the ring's or the caller's stream, and all before it
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        if (h->d_taps) (void)hipFree(h->d_taps);
+        if (h->d_hist[0]) (void)hipFree(h->d_hist[0]);
+        if (h->d_raw) (void)hipFree(h->d_raw);
+        for (int i = 0; i < COND_NSTAGE; i++)
+            {
+                if (h->d_stage[i]) (void)hipFree(h->d_stage[i]);
+                if (h->stage_done[i]) (void)hipEventDestroy(h->stage_done[i]);
+            }
+        if (h->hist_ev) (void)hipEventDestroy(h->hist_ev);
+        if (h->ev0) (void)hipEventDestroy(h->ev0);
+        if (h->ev1) (void)hipEventDestroy(h->ev1);
+        if (h->stream) (void)hipStreamDestroy(h->stream);
+        delete h;
+    }
+
+    int gsh_cond_bind(gsh_cond_t* h, gsh_stream_t* ring)
+    {
+        GSH_REQUIRE(h != nullptr, "null conditioner");
+        GSH_REQUIRE(ring == nullptr || ring->device == h->device, "the ring lies on device %d, the conditioner on device %d", ring ? ring->device : 0, h->device);
+        h->ring = ring;
+        // output n_out_total, the next one, goes to the ring's next index
+        h->ring_base = ring ? ring->next - h->n_out_total : 0ull;
+        return GSH_OK;
+    }
+
+    int gsh_cond_position(const gsh_cond_t* h, uint64_t* n_in_total, uint64_t* n_out_total)
+    {
+        GSH_REQUIRE(h != nullptr, "null conditioner");
+        if (n_in_total) *n_in_total = h->n_in_total;
+        if (n_out_total) *n_out_total = h->n_out_total;
+        return GSH_OK;
+    }
+
+    int gsh_cond_push_device(gsh_cond_t* h, const void* device_items, uint64_t n_in, void* hip_stream, uint64_t* first_out, uint64_t* n_out)
+    {
+        unsigned long long bytes = 0, count = 0;
+        int rc = check_push(h, device_items, n_in, &bytes, &count);
+        if (rc != GSH_OK) return rc;
+        const size_t align = h->plan.kind == gsh::COND_PACKED ? 1 : h->plan.item_bytes;
+        GSH_REQUIRE(n_in == 0 || reinterpret_cast<uintptr_t>(device_items) % align == 0, "the block must be aligned to its item (%zu bytes)", align);
+        report(h, count, first_out, n_out);
+        if (n_in == 0) return GSH_OK;
+        GSH_HIP(hipSetDevice(h->device));
+        hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->ring->stream;
+        rc = push_block(h, device_items, n_in, count, st);
+        if (rc != GSH_OK) return rc;
+        if (!hip_stream) GSH_HIP(hipStreamSynchronize(st));
+        return GSH_OK;
+    }
+
+    int gsh_cond_push(gsh_cond_t* h, const void* items, uint64_t n_in, uint64_t* first_out, uint64_t* n_out)
+    {
+        // the raw block crosses PCIe once, into the handle's staging buffer; one pass over it writes the ring
+        unsigned long long bytes = 0, count = 0;
+        int rc = check_push(h, items, n_in, &bytes, &count);
+        if (rc != GSH_OK) return rc;
+        report(h, count, first_out, n_out);
+        if (n_in == 0) return GSH_OK;
+        GSH_HIP(hipSetDevice(h->device));
+        hipStream_t st = h->ring->stream;
+        rc = grow(&h->d_raw, &h->raw_cap, bytes);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipMemcpyAsync(h->d_raw, items, bytes, hipMemcpyHostToDevice, st));
+        rc = push_block(h, h->d_raw, n_in, count, st);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipStreamSynchronize(st));
+        return GSH_OK;
+    }
+
+    int gsh_cond_push_pinned_async(gsh_cond_t* h, const void* items, uint64_t n_in, uint64_t* first_out, uint64_t* n_out)
+    {
+        // page-locked block -> device staging (DMA straight out of the caller's memory) -> the fused launch; nothing waits here but for the launch that
+        // read this staging buffer four pushes ago
+        unsigned long long bytes = 0, count = 0;
+        int rc = check_push(h, items, n_in, &bytes, &count);
+        if (rc != GSH_OK) return rc;
+        report(h, count, first_out, n_out);
+        if (n_in == 0) return GSH_OK;
+        GSH_HIP(hipSetDevice(h->device));
+        hipStream_t st = h->ring->stream;
+        const int slot = h->stage_next;
+        if (h->stage_done[slot] == nullptr)
+            GSH_HIP(hipEventCreateWithFlags(&h->stage_done[slot], hipEventDisableTiming));
+        else
+            GSH_HIP(hipEventSynchronize(h->stage_done[slot]));
+        rc = grow(&h->d_stage[slot], &h->stage_cap[slot], bytes);
+        if (rc != GSH_OK) return rc;
+        h->stage_next = (slot + 1) % COND_NSTAGE;
+        GSH_HIP(hipMemcpyAsync(h->d_stage[slot], items, bytes, hipMemcpyHostToDevice, st));
+        rc = push_block(h, h->d_stage[slot], n_in, count, st);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipEventRecord(h->stage_done[slot], st));
+        return GSH_OK;
+    }
+
+    int gsh_cond_time_push(gsh_cond_t* h, const void* device_block, uint64_t n_in, int reps, float* avg_ms)
+    {
+        GSH_REQUIRE(h != nullptr && avg_ms != nullptr && device_block != nullptr, "null argument");
+        GSH_REQUIRE(n_in >= 1 && reps >= 1, "%llu samples x %d", static_cast<unsigned long long>(n_in), reps);
+        unsigned long long bytes = 0;
+        int rc = block_bytes(h, n_in, &bytes);
+        if (rc != GSH_OK) return rc;
+        const unsigned long long count = outputs_after(h->plan, h->n_in_total + n_in) - h->n_out_total;
+        GSH_REQUIRE(count >= 1 && count < (1ull << 32), "a block of %llu samples completes %llu outputs: nothing to time", static_cast<unsigned long long>(n_in), count);
+        GSH_HIP(hipSetDevice(h->device));
+        // the launches of a push, into a scratch destination instead of the ring; the history update lands in the half no push has flipped to
+        float2* d_out = nullptr;
+        GSH_HIP(hipMalloc(&d_out, sizeof(float2) * count));
+        CondArgs a = block_args(h, device_block, n_in);
+        a.out = d_out;
+        a.out0 = h->n_out_total;
+        a.n_out = count;
+        gsh::cond_plan_resampler(&a);
+        hipStream_t st = h->stream;
+        hipError_t e = hipSuccess;
+        if (h->hist_recorded && (e = hipStreamWaitEvent(st, h->hist_ev, 0)) != hipSuccess) rc = gsh::hip_fail(e, "hipStreamWaitEvent", __FILE__, __LINE__);
+        auto once = [&]() {
+            int r = gsh::cond_launch(a, st);
+            if (r == GSH_OK && h->plan.n_taps > 1) r = gsh::cond_launch_history(a, st);
+            return r;
+        };
+        float ms = 0.0f;
+        for (int i = 0; i < 3 && rc == GSH_OK; i++) rc = once();  // clocks up
+        if (rc == GSH_OK && (e = hipEventRecord(h->ev0, st)) != hipSuccess) rc = gsh::hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+        for (int i = 0; i < reps && rc == GSH_OK; i++) rc = once();
+        if (rc == GSH_OK && (e = hipEventRecord(h->ev1, st)) != hipSuccess) rc = gsh::hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+        if (rc == GSH_OK && (e = hipEventSynchronize(h->ev1)) != hipSuccess) rc = gsh::hip_fail(e, "hipEventSynchronize", __FILE__, __LINE__);
+        if (rc == GSH_OK && (e = hipEventElapsedTime(&ms, h->ev0, h->ev1)) != hipSuccess) rc = gsh::hip_fail(e, "hipEventElapsedTime", __FILE__, __LINE__);
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(d_out);
+        if (rc != GSH_OK) return rc;
+        *avg_ms = ms / static_cast<float>(reps);
+        return GSH_OK;
+    }
+}

@@ -12,6 +12,7 @@
 // it stages the translated inputs its tile needs (tile * D + K - 1 samples) in LDS once, then every thread forms its outputs from LDS with
 // the taps read as wave-uniform LDS broadcasts.
 #include "gsh_internal.h"
+#include "conditioner.h"
 #include "packed_unpack.h"
 #include <cmath>
 #include <new>
@@ -154,6 +155,194 @@ __global__ void fir_history_kernel(FirArgs a)
         }
 }
 }  // namespace
+}  // namespace gsh
+
+// ---- the signal conditioner's kernels (conditioner.h): adapter -> this filter -> direct resampler, one thread per ring sample.  They sit here to
+// call fetch_translated and to repeat fir_kernel's sum, so that a ring sample has the bits the loose chain gives it.
+namespace gsh
+{
+namespace
+{
+template <typename T>
+struct alignas(2 * sizeof(T)) CondPair
+{
+    T i, q;
+};
+
+// sample with absolute index n of the conditioner's input stream, decoded and conjugated as the adapter in front of the filter leaves it
+// (sample_convert.hip, packed_unpack.hip: integer -> float cast, Q times -1 for inverted_spectrum); not translated
+__device__ __forceinline__ float2 cond_sample(const CondArgs& a, long long n)
+{
+    if (n < 0) return make_float2(0.0f, 0.0f);
+    const long long rel = n - static_cast<long long>(a.in0);
+    if (rel < 0)
+        {
+            const long long h = (a.n_taps - 1) + rel;  // hist[K - 2] is sample in0 - 1
+            return h >= 0 ? a.hist[h] : make_float2(0.0f, 0.0f);
+        }
+    if (static_cast<unsigned long long>(rel) >= a.n_in) return make_float2(0.0f, 0.0f);  // (the host's count never asks for it)
+    const unsigned long long i = static_cast<unsigned long long>(rel);
+    float2 x;
+    switch (a.kind)
+        {
+        case COND_PACKED:
+            x = packed_sample(static_cast<const unsigned char*>(a.in), a.packed, i);
+            break;
+        case COND_CPX_SHORT:
+            {
+                const CondPair<short> p = static_cast<const CondPair<short>*>(a.in)[i];
+                x = make_float2(static_cast<float>(p.i), static_cast<float>(p.q));
+                break;
+            }
+        case COND_CPX_BYTE:
+            {
+                const CondPair<signed char> p = static_cast<const CondPair<signed char>*>(a.in)[i];
+                x = make_float2(static_cast<float>(p.i), static_cast<float>(p.q));
+                break;
+            }
+        default:
+            x = load_item(a.in, i, a.kind);
+            break;
+        }
+    if (a.conj) x.y = -1.0f * x.y;
+    return x;
+}
+
+// the same sample moved to baseband: fetch_translated itself, handed the converted sample as a one-sample complex block that starts at n
+__device__ __forceinline__ float2 cond_translated(const CondArgs& a, long long n)
+{
+    const float2 x = cond_sample(a, n);
+    FirArgs t;
+    t.in = &x;
+    t.hist = nullptr;
+    t.in0 = static_cast<unsigned long long>(n < 0 ? 0 : n);
+    t.rev_per_sample = a.rev_per_sample;
+    t.n_taps = 1;
+    t.in_kind = 0;
+    return fetch_translated<false>(t, n);
+}
+
+// filter output that feeds output d of the launch: resample_gather_kernel's index (resampler.hip), d below 2^32
+__device__ __forceinline__ unsigned long long cond_filter_index(const CondArgs& a, unsigned long long d)
+{
+    if (a.rs_mode == COND_RS_DECIMATE) return a.q0 + (a.r0 + (d << 32)) / a.step;
+    if (a.rs_mode == COND_RS_INTERPOLATE) return a.q0 + ((a.r0 + d * a.step) >> 32);
+    return a.out0 + d;
+}
+
+// A work-group stages the translated inputs of its tile of ring samples once -- from filter output m_first = m(tile0) to m_last = m(tile0 + cnt - 1),
+// (m_last - m_first) D + K samples -- and forms only the filter outputs the resampler keeps, each with fir_kernel's ascending-k fmaf chain.
+__global__ __launch_bounds__(FIR_THREADS) void cond_fir_kernel(CondArgs a)
+{
+    extern __shared__ __align__(16) float2 lds[];
+    float* ltaps = reinterpret_cast<float*>(lds);           // n_taps floats (rounded up to an even count)
+    float2* lx = lds + ((a.n_taps + 1) >> 1);
+    const int K = a.n_taps, D = a.decimation;
+    for (int i = threadIdx.x; i < K; i += FIR_THREADS) ltaps[i] = a.taps[i];
+    for (unsigned long long tile0 = static_cast<unsigned long long>(blockIdx.x) * a.tile; tile0 < a.n_out; tile0 += static_cast<unsigned long long>(gridDim.x) * a.tile)
+        {
+            const int cnt = static_cast<int>(min(static_cast<unsigned long long>(a.tile), a.n_out - tile0));
+            const unsigned long long m_first = cond_filter_index(a, tile0);
+            const unsigned long long m_last = cond_filter_index(a, tile0 + cnt - 1);
+            // filter output m needs inputs m D - K + 1 .. m D
+            const long long first = static_cast<long long>(m_first * D) - (K - 1);
+            const int span = static_cast<int>(min((m_last - m_first) * D + K, static_cast<unsigned long long>(a.max_span)));
+            __syncthreads();
+            for (int i = threadIdx.x; i < span; i += FIR_THREADS) lx[i] = cond_translated(a, first + i);
+            __syncthreads();
+            for (int j = threadIdx.x; j < cnt; j += FIR_THREADS)
+                {
+                    const unsigned long long off = (cond_filter_index(a, tile0 + j) - m_first) * D;
+                    if (off + K > static_cast<unsigned long long>(span)) continue;  // (cond_tile bounds the span: never taken)
+                    // y = sum_k h[k] x[mD - k]; x[mD - k] sits at lx[off + (K - 1) - k]
+                    const float2* xp = lx + off + (K - 1);
+                    float re = 0.0f, im = 0.0f;
+                    for (int k = 0; k < K; k++)
+                        {
+                            const float h = ltaps[k];
+                            const float2 v = xp[-k];
+                            re = fmaf(h, v.x, re);
+                            im = fmaf(h, v.y, im);
+                        }
+                    a.out[tile0 + j] = make_float2(re, im);
+                }
+        }
+}
+
+// no filter: the ring sample is the converted input sample the resampler picks, as it is (no sum, so that -0 stays -0)
+__global__ __launch_bounds__(FIR_THREADS) void cond_copy_kernel(CondArgs a)
+{
+    const unsigned long long stride = static_cast<unsigned long long>(gridDim.x) * FIR_THREADS;
+    for (unsigned long long d = static_cast<unsigned long long>(blockIdx.x) * FIR_THREADS + threadIdx.x; d < a.n_out; d += stride)
+        a.out[d] = cond_sample(a, static_cast<long long>(cond_filter_index(a, d)));
+}
+
+// keep the last K - 1 input samples (converted, untranslated) for the next push: fir_history_kernel with the conditioner's decode
+__global__ void cond_history_kernel(CondArgs a)
+{
+    const int K1 = a.n_taps - 1;
+    const long long end = static_cast<long long>(a.in0 + a.n_in);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < K1; i += gridDim.x * blockDim.x) a.hist_out[i] = cond_sample(a, end - K1 + i);
+}
+}  // namespace
+
+void cond_plan_resampler(CondArgs* a)
+{
+    a->q0 = a->r0 = 0;
+    if (a->rs_mode == COND_RS_DECIMATE)
+        {
+            const unsigned __int128 A = (static_cast<unsigned __int128>(a->out0) << 32) + a->step - 1;
+            a->q0 = static_cast<unsigned long long>(A / a->step);
+            a->r0 = static_cast<unsigned long long>(A % a->step);
+        }
+    else if (a->rs_mode == COND_RS_INTERPOLATE)
+        {
+            const unsigned __int128 B = static_cast<unsigned __int128>(a->out0 + 1) * a->step;
+            a->q0 = static_cast<unsigned long long>(B >> 32);
+            a->r0 = static_cast<unsigned long long>(B & 0xffffffffu);
+        }
+}
+
+void cond_tile(CondArgs* a)
+{
+    // t consecutive ring samples reach over at most gap(t) filter outputs: m(d + t - 1) - m(d) <= floor((t - 1) / ratio) + 1 with the resampler, t - 1 without
+    const int K = a->n_taps < 1 ? 1 : a->n_taps;
+    auto span_of = [&](unsigned long long t) {
+        unsigned long long gap = t - 1;
+        if (a->rs_mode == COND_RS_DECIMATE) gap = (((t - 1) << 32) / a->step) + 1;
+        if (a->rs_mode == COND_RS_INTERPOLATE) gap = (((t - 1) * a->step) >> 32) + 1;
+        return gap * static_cast<unsigned long long>(a->decimation) + K;
+    };
+    int tile = COND_TILE;
+    while (tile > 1 && span_of(tile) > static_cast<unsigned long long>(COND_MAX_SPAN)) tile >>= 1;  // (one output spans K <= FIR_MAX_TAPS inputs)
+    a->tile = tile;
+    a->max_span = static_cast<int>(span_of(tile));
+}
+
+int cond_launch(const CondArgs& a, hipStream_t st)
+{
+    if (a.n_taps == 0)
+        {
+            unsigned long long blocks = (a.n_out + FIR_THREADS - 1) / FIR_THREADS;
+            if (blocks > 256ull * 16ull) blocks = 256ull * 16ull;
+            cond_copy_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(FIR_THREADS), 0, st>>>(a);
+            GSH_HIP(hipGetLastError());
+            return GSH_OK;
+        }
+    const size_t lds = sizeof(float2) * (static_cast<size_t>(a.max_span) + ((a.n_taps + 1) >> 1));  // at most 32 KiB + 4 KiB
+    unsigned long long blocks = (a.n_out + a.tile - 1) / a.tile;
+    if (blocks > 256ull * 8ull) blocks = 256ull * 8ull;
+    cond_fir_kernel<<<dim3(static_cast<unsigned>(blocks)), dim3(FIR_THREADS), lds, st>>>(a);
+    GSH_HIP(hipGetLastError());
+    return GSH_OK;
+}
+
+int cond_launch_history(const CondArgs& a, hipStream_t st)
+{
+    cond_history_kernel<<<dim3(4), dim3(256), 0, st>>>(a);
+    GSH_HIP(hipGetLastError());
+    return GSH_OK;
+}
 }  // namespace gsh
 
 namespace gsh

@@ -11,6 +11,7 @@
 // -- an exact integer gather, independent of how the stream is cut into work() calls.  HBM-bound: 8 bytes in (of the samples that are
 // kept) + 8 bytes out per output sample.
 #include "gsh_internal.h"
+#include "resample_index.h"
 #include <cmath>
 
 namespace gsh
@@ -42,24 +43,6 @@ __global__ __launch_bounds__(RS_THREADS) void resample_gather_kernel(ResampleArg
                 i = a.q0 + ((a.r0 + d * a.step) >> 32);          // floor((B0 + d step) / 2^32), B0 = (out0 + 1) step
             a.dst[d] = a.src[i - a.in0];
         }
-}
-
-// phase step exactly as the reference computes it (:52-59); 0 stands for a ratio of one (2^32 does not fit the uint32 cast)
-unsigned phase_step_of(double fs_in, double fs_out, int* decimating)
-{
-    const double two_32 = 4294967296.0;
-    *decimating = fs_in >= fs_out ? 1 : 0;
-    const double v = *decimating ? std::floor(two_32 * fs_out / fs_in) : std::floor(two_32 * fs_in / fs_out);
-    if (v >= two_32) return 0u;
-    return static_cast<unsigned>(v);
-}
-
-// absolute input index feeding absolute output j
-unsigned long long input_index_of(unsigned long long j, unsigned step, int decimating)
-{
-    if (step == 0) return j;
-    if (decimating) return static_cast<unsigned long long>(((static_cast<unsigned __int128>(j) << 32) + step - 1) / step);
-    return static_cast<unsigned long long>((static_cast<unsigned __int128>(j + 1) * step) >> 32);
 }
 }  // namespace
 }  // namespace gsh

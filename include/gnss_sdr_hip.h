@@ -541,6 +541,67 @@ extern "C"
      * (real families: input_kind 1 with the floats of gsh_unpack_device; complex families: input_kind 0, not conjugated). */
     int gsh_fir_create_packed(int device, const float* taps, int n_taps, int decimation, double center_freq_hz, double sampling_freq_hz,
         const gsh_packed_format* fmt, gsh_fir_t** out);
+    /* ---- signal conditioner: the chain every receiver puts between its source and its channels (Signal_Conditioner,
+     * src/algorithms/conditioner/adapters/signal_conditioner.cc:60-87: DataTypeAdapter -> InputFilter -> Resampler), one handle and one call per
+     * block, one pass over the raw block straight into a ring.  Ring sample j of the conditioner's output (j counts from the handle's creation) is
+     *   ring[base + j] = sum_{k<K} taps[k] rot(x[m(j) D - k]),
+     * x the block's samples decoded as the adapters decode them (ibyte_to_complex.cc:45-51, ishort_to_complex.cc:45-51, the packed sources
+     * above; conjugated first when inverted_spectrum), rot and the sum those of gsh_fir_process_device (freq_xlating_fir_filter.cc:115-161,
+     * fir_filter.cc), m(j) the input index of gsh_direct_resample_device (direct_resampler_conditioner_cc.cc:39-129), `base` the ring's next index
+     * when it was bound.  Invariant: after any sequence of pushes the ring holds, index for index and bit for bit, what gsh_convert_samples_device
+     * / gsh_unpack_device -> gsh_fir_process_device -> gsh_direct_resample_device give for the concatenated input in one call per stage; where the
+     * stream is cut into pushes does not matter.  Only the filter outputs the resampler keeps are formed.  The handle owns its device staging
+     * and the converted history (n_taps - 1 samples) between pushes; all counts are integers computed on the host, a push reads nothing back.
+     * Not stages of this chain (they stay loose calls): Pulse_Blanking_Filter, Notch_Filter, Notch_Filter_Lite (gsh_pb_*, gsh_notch_*: sequential
+     * per-segment state); a fan-out of several filters into several rings; stream groups; the cshort / cbyte outputs of the xlating adapter
+     * (freq_xlating_fir_filter.cc:136-160). */
+#define GSH_COND_INPUT_ITEMS 0  /* complex items of an enum gsh_item_type (item_type) */
+#define GSH_COND_INPUT_REAL 1   /* real items: item_type 1 float32, 2 int16, 3 int8 (the input_kind of gsh_fir_create); needs a filter */
+#define GSH_COND_INPUT_PACKED 2 /* packed front-end bytes (packed); a real family needs a filter */
+    typedef struct
+    {
+        int32_t input;             /* GSH_COND_INPUT_* */
+        int32_t item_type;         /* see GSH_COND_INPUT_ITEMS / _REAL; unused for packed input */
+        int32_t inverted_spectrum; /* conjugate the decoded sample before the filter (complex input only) */
+        int32_t n_taps;            /* 0: InputFilter Pass_Through; else 1..1024 as gsh_fir_create */
+        const float* taps;         /* n_taps real taps (copied by gsh_cond_create) */
+        int32_t decimation;        /* 1..64; 0 reads as 1 */
+        int32_t reserved;          /* 0 */
+        double center_freq_hz;     /* IF */
+        double sampling_freq_hz;   /* of the filter's input; positive when n_taps > 0 */
+        double fs_in, fs_out;      /* Direct_Resampler: sample_freq_in (the rate after the filter) / sample_freq_out; both 0: Pass_Through */
+        gsh_packed_format packed;  /* GSH_COND_INPUT_PACKED */
+    } gsh_cond_conf;
+    typedef struct gsh_cond gsh_cond_t;
+    /* GSH_ERR_INVALID with a message, before any device is touched, for: a null pointer, an unknown input or item type, real input without a
+     * filter (the ring holds complex samples), inverted_spectrum on real input, taps / decimation / sampling frequency outside gsh_fir_create's
+     * limits, one of fs_in / fs_out zero or negative, a ratio the 32-bit phase accumulator cannot hold (as gsh_direct_resample_device), a bad
+     * packed format */
+    int gsh_cond_create(int device, const gsh_cond_conf* conf, gsh_cond_t** out);
+    void gsh_cond_destroy(gsh_cond_t* h);
+    /* the same checks and the bookkeeping alone, no GPU: *n_out_total = ring samples the conditioner has produced once n_in_total input samples
+     * have arrived (every filter output whose newest input is there, every resampler output whose filter output is) */
+    int gsh_cond_plan(const gsh_cond_conf* conf, uint64_t n_in_total, uint64_t* n_out_total);
+    /* the ring the pushes write (on the handle's device; it outlives the handle's use): the conditioner's NEXT output goes to the ring's next
+     * index as it stands now.  NULL detaches. */
+    int gsh_cond_bind(gsh_cond_t* h, gsh_stream_t* ring);
+    /* One block of n_in input samples (packed input: a whole number of input items) through the chain into the bound ring.  *first_out = ring
+     * index of the block's first output, *n_out = how many it completed (0 is not an error: a block shorter than the decimation); either may be
+     * NULL.  gsh_cond_push: host memory, synchronous.  _push_device: the block lies in device memory (aligned to its item), the work is queued on
+     * hip_stream (NULL: the ring's own stream, synchronous).  _push_pinned_async: page-locked host memory (gsh_host_register), returns at once;
+     * the block must stay untouched until gsh_stream_wait_copied / gsh_stream_wait_copied_upto(ring, *first_out + *n_out) covers the push (a
+     * push with *n_out = 0: until the next one is covered).
+     * All or nothing; a refusal advances nothing and rotates no history: GSH_ERR_INVALID for more outputs than the ring's capacity, a partial
+     * packed item, no bound ring; GSH_ERR_STATE when the ring's next index is no longer where the conditioner left it (someone else pushed or
+     * sought) or a live tracking channel would be overrun. */
+    int gsh_cond_push(gsh_cond_t* h, const void* items, uint64_t n_in, uint64_t* first_out, uint64_t* n_out);
+    int gsh_cond_push_device(gsh_cond_t* h, const void* device_items, uint64_t n_in, void* hip_stream, uint64_t* first_out, uint64_t* n_out);
+    int gsh_cond_push_pinned_async(gsh_cond_t* h, const void* items, uint64_t n_in, uint64_t* first_out, uint64_t* n_out);
+    /* input samples taken and ring samples produced since the handle was created */
+    int gsh_cond_position(const gsh_cond_t* h, uint64_t* n_in_total, uint64_t* n_out_total);
+    /* average HIP-event time of the device work of one push of device_block (n_in samples, device memory) from the handle's present state: the
+     * fused launch into a scratch destination and the history update.  Neither the ring nor the handle's position or history changes. */
+    int gsh_cond_time_push(gsh_cond_t* h, const void* device_block, uint64_t n_in, int reps, float* avg_ms);
     /* bind a bank to a ring: from now on gsh_corr_job.sample_offset is an ABSOLUTE sample index; a job whose window is not
      * fully resident (or longer than max_window_samples) fails with GSH_ERR_INVALID.  NULL detaches.
      * Residency is checked when the job table is staged (gsh_bank_correlate / gsh_bank_upload_jobs): a table uploaded once and
