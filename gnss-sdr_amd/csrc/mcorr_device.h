@@ -65,6 +65,10 @@ constexpr int MC_HALF_WORDS = 2 * (MC_HALF_MAX_CODE_LEN + 2 * MC_MARGIN);  // 2 
 #ifndef GSH_MC_RUNLEN
 #define GSH_MC_RUNLEN 1  // the paired trips of a segment as counted runs (run_segment_packed); 0: the trip kind asked before every trip, rounds 2 - 6
 #endif
+#ifndef GSH_MC_TRIP_PAIRS
+#define GSH_MC_TRIP_PAIRS 1  // a run of paired trips takes two trips per pass of its loop where it can: one load base, one step per counter, one back-edge for both
+                             // (run_segment_packed, round 9; 0: one trip per pass)
+#endif
 #ifndef GSH_MC_DER_MIXED
 #define GSH_MC_DER_MIXED 0  // 1: in a trip with one unsafe chunk the other chunk still pairs its taps (two more loop bodies: measured, the register
                             // allocator then spills and the launch is 45 % slower -- profiles/r02/paired_taps.txt)
@@ -987,6 +991,31 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
 #endif
             }
     };
+    // TRIP PAIRS (round 9): two plain trips per pass of a run's loop share ONE scalar base, a running pointer to the middle of the two trips whose loads they issue; the
+    // four chunks lie at -24 / -8 / +8 / +24 PPC bytes around it, inside the 13-bit immediate offset of global_load up to 128 threads (+-3072 beside +-1024).
+    // (the half-chip flavour only: the other paired-tap flavours stay as they are)
+#ifdef GSH_EXP_NOLOAD
+    constexpr bool PAIRS = false;
+#else
+    constexpr bool PAIRS = GSH_MC_TRIP_PAIRS && HALF && NCH == 2 && PF == 1 && (24 * PPC <= 4095);
+#endif
+    global_bytes pair_ptr = nullptr;
+    auto load_pair = [&](auto second, float4& va, float4& vb, v2f y0, v2f y1, v2f y2, v2f y3) {
+        // (the rotated samples are inputs of the empty asm: without a branch in front of them the loads would otherwise be hoisted above the rotations, into registers
+        //  of their own -- two trips of samples in flight, five more VGPRs: ISA, round 9.  The queue stays one deep.)
+        asm volatile("" : "+v"(lane_bytes) : "v"(y0), "v"(y1), "v"(y2), "v"(y3));
+        const global_bytes mid = pair_ptr + lane_bytes;
+        if constexpr (decltype(second)::value)
+            {
+                va = load16(mid + 8 * PPC);
+                vb = load16(mid + 24 * PPC);
+            }
+        else
+            {
+                va = load16(mid - 24 * PPC);
+                vb = load16(mid - 8 * PPC);
+            }
+    };
     auto load_edge = [&](int i, float4& va, float4& vb) {
             {
                 const int n0 = lane_n0(i);
@@ -1197,12 +1226,15 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
     if constexpr (!EARLY_LOADS) first_loads();
     v2f pa = zero, nfA = zero, nfB = zero;
     int until_reseed = 0, r_idx = 0, tbl0 = 0;
+    using std::integral_constant;
     // one trip; j: its slot in the load queue; FA / FB (compile time): chunk A / B reads its early tap next to the late one
-    auto trip = [&](int i, auto jc, auto fa, auto fb, auto kp) {
+    // (pm, optional: 1 / 2 -- the first / second trip of a pair, see PAIRS: both issue plain loads off pair_ptr, and the second never re-seeds -- the caller vouches)
+    auto trip = [&](int i, auto jc, auto fa, auto fb, auto kp, auto... pm) {
+        constexpr int PM = (0 + ... + decltype(pm)::value);
         constexpr int j = decltype(jc)::value;
         constexpr bool FA = decltype(fa)::value, FB = decltype(fb)::value;
         constexpr bool KP = decltype(kp)::value;  // the caller knows that trip i is a plain one (first_plain <= i < last_plain)
-        if (until_reseed == 0)  // uniform: exact re-seed of the lane's phasor and of (float)n
+        if (PM != 2 && until_reseed == 0)  // uniform: exact re-seed of the lane's phasor and of (float)n
             {
                 const int n0 = lane_n0(i);
                 if (!single && !fac && r_idx - tbl0 >= TBL)
@@ -1274,7 +1306,9 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
                     }
             }
 #if GSH_MC_RUNLEN
-        if constexpr ((FA && (FB || NCH == 1)) || KP)
+        if constexpr (PM != 0)
+            load_pair(integral_constant<bool, PM == 2>{}, qa[j], qb[j], yA0, yA1, yB0, yB1);
+        else if constexpr ((FA && (FB || NCH == 1)) || KP)
             {
                 // (a paired trip is a plain one: the trip PF ahead lies at or beyond the first plain trip, and one comparison says whether it is plain itself)
                 if (i + PF < last_plain)  // uniform
@@ -1303,7 +1337,6 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
         asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfA) : "s"(stride));
         if (NCH == 2) asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfB) : "s"(stride));
     };
-    using std::integral_constant;
     using no = integral_constant<bool, false>;
     using yes = integral_constant<bool, true>;
     if constexpr (DER)
@@ -1353,6 +1386,33 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
                     int run = paired_run(i);
                     while (run > 0)
                         {
+                            if constexpr (PAIRS)
+                                {
+                                    // pairs from i on: both trips in the run, the trip whose loads the second one issues (i + 2) still plain, and no re-seed on a
+                                    // second trip (the trips left to the re-seed stay even once they are: an odd count ends the pairs one trip before it)
+                                    int np = min(run, last_plain - 1 - i) >> 1;
+                                    if (until_reseed & 1) np = min(np, until_reseed >> 1);
+                                    if (np > 0)  // uniform
+                                        {
+                                            pair_ptr = trip_base(i + 1, 24 * PPC);
+                                            run -= 2 * np;
+                                            do
+                                                {
+                                                    trip(i, j0{}, yes{}, yes{}, no{}, integral_constant<int, 1>{});
+                                                    // (the two trips one after the other: left to interleave them the scheduler starts the second trip's chains under the
+                                                    //  first one's accumulates and the kernel needs 90 VGPRs instead of 82 -- ISA, round 9)
+                                                    __builtin_amdgcn_sched_barrier(0);
+                                                    trip(i + 1, j0{}, yes{}, yes{}, no{}, integral_constant<int, 2>{});
+                                                    i += 2;
+                                                    pair_ptr += 2 * TRIP * static_cast<int>(sizeof(float2));
+                                                    asm("" : "+s"(pair_ptr));
+                                                    np--;
+                                                }
+                                            while (np > 0);
+                                            if (run == 0) run = paired_run(i);  // uniform
+                                            continue;
+                                        }
+                                }
                             trip(i, j0{}, yes{}, integral_constant<bool, NCH == 2>{}, no{});
                             i++;
                             run--;
