@@ -13,3 +13,4 @@ from . import _lib  # noqa: F401
 from ._lib import GSH_MAX_TAPS, GshError, load  # noqa: F401
 from .build import build_library  # noqa: F401
 from .conditioner import SignalConditioner  # noqa: F401
+from .signal_generator import SignalGenerator  # noqa: F401

@@ -205,6 +205,7 @@ class AcqResult(C.Structure):
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _I16 = C.POINTER(C.c_int16)
+_I8 = C.POINTER(C.c_int8)
 SYMBOLS = {
     "gsh_abi_version": (C.c_int, []),
     "gsh_device_count": (C.c_int, []),
@@ -324,6 +325,17 @@ SYMBOLS = {
     "gsh_cond_push_pinned_async": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsh_cond_position": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsh_cond_time_push": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _F]),
+    "gsh_gen_create": (C.c_int, [C.c_int, C.c_double, C.c_int32, C.POINTER(_P)]),
+    "gsh_gen_destroy": (None, [_P]),
+    "gsh_gen_set_satellite": (C.c_int, [_P, C.c_int32, _F, _F, C.c_uint32, C.c_uint32, _I8, C.c_int32, _I8, C.c_int32, C.c_double, C.c_double, C.c_double]),
+    "gsh_gen_check_satellite": (C.c_int, [C.c_double, _F, _F, C.c_uint32, C.c_uint32, _I8, C.c_int32, _I8, C.c_int32, C.c_double, C.c_double, C.c_double]),
+    "gsh_gen_set_noise": (C.c_int, [_P, C.c_int32, C.c_uint64]),
+    "gsh_gen_seek": (C.c_int, [_P, C.c_uint64]),
+    "gsh_gen_position": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "gsh_gen_generate_device": (C.c_int, [_P, C.c_uint64, _P]),
+    "gsh_gen_push": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gsh_gen_time_generate": (C.c_int, [_P, C.c_uint64, C.c_int, _F]),
+    "gsh_gen_philox_words": (None, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
     "gsh_trk_create": (C.c_int, [C.c_int, C.POINTER(TrkConf), C.c_int, C.c_int, C.POINTER(_P)]),
     "gsh_trk_destroy": (None, [_P]),
     "gsh_trk_set_stream_host": (C.c_int, [_P, _F, C.c_uint64]),

@@ -602,6 +602,55 @@ extern "C"
     /* average HIP-event time of the device work of one push of device_block (n_in samples, device memory) from the handle's present state: the
      * fused launch into a scratch destination and the history update.  Neither the ring nor the handle's position or history changes. */
     int gsh_cond_time_push(gsh_cond_t* h, const void* device_block, uint64_t n_in, int reps, float* avg_ms);
+    /* ---- signal generator: synthetic GNSS scenarios made on the device (Signal_Generator: src/algorithms/signal_generator/adapters/
+     * signal_generator.cc over gnuradio_blocks/signal_generator_c.h / .cc = sg.cc), into a caller's device buffer or straight into a ring.
+     * Table-driven.  A generator holds n_sats <= GSH_GEN_MAX_SATS satellites; a satellite is two complex64 tables A and B of `period` samples
+     * (B may be NULL), a delay_samples in [0, period), two periodic sign sequences sA, sB of 1..GSH_GEN_MAX_SIGNS bytes +-1, and a carrier.
+     * Sample n -- the ABSOLUTE index since the generator's start -- is, in float32, satellites in ascending order, every operation rounded once:
+     *   out[n] = sum_sat (sA[p mod len_a] A[n mod period] + sB[p mod len_b] B[n mod period]) exp(+j (start_phase + 2 pi f n / fs)) + noise[n]
+     *   p = (n + period - delay_samples) / period   (the sign boundaries passed: one lies at every n = delay_samples mod period, where the
+     *       reference may change its data bit inside a code period, sg.cc:362-383, :426-450)      f = doppler_hz + carrier_offset_hz
+     * which covers the reference's three combinations: GPS / GLONASS (sg.cc:366, :399: A = scaled sampled code, sA = data bits, no B; GLONASS'
+     * FDMA offset, sg.cc:388, is carrier_offset_hz), Galileo E1 / E6 (sg.cc:518, :492: A = data component, B = minus the pilot with its secondary
+     * code, sB = +1) and Galileo E5a / E5b (sg.cc:428-448: A = (Re, 0), B = (0, Im), sA = data bit x I secondary code, sB = Q secondary code,
+     * an entry per code period).  The tables are the host's: generate_codes() (sg.cc:164-323) with its chip shift and its C/N0 scaling
+     * sqrt(10^(CN0/10) / BW_BB) (sg.cc:184), halved power for two-component signals (sg.cc:230); the kernel knows amplitudes only.
+     * Carrier: the phase of sample n is evaluated from n (128-bit fixed-point revolutions per sample, exact for every 64-bit index) -- the
+     * reference accumulates a float32 phase per sample and a float32 start phase per vector (sg.cc:350-354); a stated deviation.
+     * Noise (off: nothing is added): complex white Gaussian of unit variance per component (sg.cc:540-546), Philox4x32-10 keyed by the seed with
+     * the absolute sample index as its counter, then Box-Muller.  Table entry, sign, phase and noise of sample n depend on n alone: the stream is
+     * the same bit for bit however it is cut into calls and wherever a ring wraps.  The data bits the reference draws from a random_device are
+     * the caller's sign sequence. */
+#define GSH_GEN_MAX_SATS 32
+#define GSH_GEN_MAX_SIGNS 1024
+    typedef struct gsh_gen gsh_gen_t;
+    /* GSH_ERR_INVALID before any device is touched: null out, fs_sps not positive and finite, n_sats outside 1..GSH_GEN_MAX_SATS */
+    int gsh_gen_create(int device, double fs_sps, int32_t n_sats, gsh_gen_t** out);
+    void gsh_gen_destroy(gsh_gen_t* g);
+    /* tables as interleaved (I, Q) float32, copied.  GSH_ERR_INVALID before anything is touched: null handle, table A or sign sequence, `sat`
+     * outside the handle's satellites, period below 1 (or above 2^30), delay_samples outside [0, period), a sign byte other than +-1, a sequence
+     * length outside 1..GSH_GEN_MAX_SIGNS, a Doppler, start phase, carrier offset or table value that is not finite.  With table_b NULL signs_b /
+     * len_b are not read.  gsh_gen_check_satellite: the same checks alone, without a handle or a GPU. */
+    int gsh_gen_set_satellite(gsh_gen_t* g, int32_t sat, const float* table_a, const float* table_b, uint32_t period, uint32_t delay_samples,
+        const int8_t* signs_a, int32_t len_a, const int8_t* signs_b, int32_t len_b, double doppler_hz, double start_phase_rad, double carrier_offset_hz);
+    int gsh_gen_check_satellite(double fs_sps, const float* table_a, const float* table_b, uint32_t period, uint32_t delay_samples, const int8_t* signs_a,
+        int32_t len_a, const int8_t* signs_b, int32_t len_b, double doppler_hz, double start_phase_rad, double carrier_offset_hz);
+    int gsh_gen_set_noise(gsh_gen_t* g, int32_t enabled, uint64_t seed);
+    /* the next sample to produce (below 2^63) */
+    int gsh_gen_seek(gsh_gen_t* g, uint64_t sample_index);
+    int gsh_gen_position(const gsh_gen_t* g, uint64_t* sample_index);
+    /* the next n samples as complex64 at device_out (device memory, 8-byte aligned); synchronous.  GSH_ERR_STATE while a satellite is unset. */
+    int gsh_gen_generate_device(gsh_gen_t* g, uint64_t n, void* device_out);
+    /* the next n samples straight into the ring, which afterwards is what a push of those samples from the host would have left (resident range,
+     * mirror, push event and history, live words); *first_index (may be NULL) = the ring index of the first.  Synchronous.  All or nothing, the
+     * ring and the generator's position stay as they were: GSH_ERR_INVALID for a null ring, a ring on another device, n above the ring's
+     * capacity; GSH_ERR_STATE for an unset satellite or a live tracking channel whose samples the push would overwrite. */
+    int gsh_gen_push(gsh_gen_t* g, gsh_stream_t* ring, uint64_t n, uint64_t* first_index);
+    /* average HIP-event time of generating n samples (at most 2^30) from the present position into a scratch buffer; the position stays */
+    int gsh_gen_time_generate(gsh_gen_t* g, uint64_t n, int reps, float* avg_ms);
+    /* the noise's word stage on the host (csrc/signal_generator.h, the text the kernel runs): the four Philox4x32-10 words of counter
+     * (sample_index low, high, 0, 0) under key (seed low, high); I and Q of the sample come from words 0 and 1 */
+    void gsh_gen_philox_words(uint64_t seed, uint64_t sample_index, uint32_t out[4]);
     /* bind a bank to a ring: from now on gsh_corr_job.sample_offset is an ABSOLUTE sample index; a job whose window is not
      * fully resident (or longer than max_window_samples) fails with GSH_ERR_INVALID.  NULL detaches.
      * Residency is checked when the job table is staged (gsh_bank_correlate / gsh_bank_upload_jobs): a table uploaded once and
