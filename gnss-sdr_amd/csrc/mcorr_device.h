@@ -69,6 +69,14 @@ constexpr int MC_HALF_WORDS = 2 * (MC_HALF_MAX_CODE_LEN + 2 * MC_MARGIN);  // 2 
 #define GSH_MC_TRIP_PAIRS 1  // a run of paired trips takes two trips per pass of its loop where it can: one load base, one step per counter, one back-edge for both
                              // (run_segment_packed, round 9; 0: one trip per pass)
 #endif
+#ifndef GSH_MC_PAIR_QUEUE
+#define GSH_MC_PAIR_QUEUE 2  // trips of sample loads in flight inside a run of trip pairs (run_segment_packed, round 10).  2: each trip of a pair has its own four sample
+                             // registers, and the loads a trip issues are awaited two trips later; 1: round 9's loop, one trip ahead
+#endif
+#ifndef GSH_MC_PAIR_BARRIER
+#define GSH_MC_PAIR_BARRIER 1  // the scheduling barrier between the two trips of a pair with two trips of loads in flight; 0: the second trip's chains may start under the first
+                               // one's accumulates (measured, round 10, profiles/r10_summary.txt: the same 90 VGPRs, 0.1 % slower in each of seven alternating pairs)
+#endif
 #ifndef GSH_MC_DER_MIXED
 #define GSH_MC_DER_MIXED 0  // 1: in a trip with one unsafe chunk the other chunk still pairs its taps (two more loop bodies: measured, the register
                             // allocator then spills and the launch is 45 % slower -- profiles/r02/paired_taps.txt)
@@ -999,10 +1007,18 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
 #else
     constexpr bool PAIRS = GSH_MC_TRIP_PAIRS && HALF && NCH == 2 && PF == 1 && (24 * PPC <= 4095);
 #endif
+    // TWO TRIPS OF LOADS IN FLIGHT (round 10): inside a run of pairs the second trip of a pair has sample registers of its own (slot 1 of the queue), so the loads a trip
+    // issues -- those of the trip two ahead, into the registers it has just rotated out of -- have two trips' arithmetic to arrive in instead of one.  Outside a run of
+    // pairs the queue is one deep as before: the run starts with one more pair of loads (its second trip's) and its last pass issues only the first trip's, so that on
+    // leaving it exactly the next trip's loads are in flight, in slot 0.
+    constexpr bool QUEUE2 = PAIRS && (GSH_MC_PAIR_QUEUE == 2);
+    static_assert(GSH_MC_PAIR_QUEUE == 1 || GSH_MC_PAIR_QUEUE == 2, "one or two trips of loads in flight in a run of pairs");
+    constexpr int NQ = PF + (QUEUE2 ? 1 : 0);
     global_bytes pair_ptr = nullptr;
     auto load_pair = [&](auto second, float4& va, float4& vb, v2f y0, v2f y1, v2f y2, v2f y3) {
         // (the rotated samples are inputs of the empty asm: without a branch in front of them the loads would otherwise be hoisted above the rotations, into registers
-        //  of their own -- two trips of samples in flight, five more VGPRs: ISA, round 9.  The queue stays one deep.)
+        //  of their own -- two trips of samples in flight, five more VGPRs: ISA, round 9.  A trip's loads go into the registers it has rotated out of, whether the
+        //  queue is one trip deep or, inside a run of pairs, two: QUEUE2 below.)
         asm volatile("" : "+v"(lane_bytes) : "v"(y0), "v"(y1), "v"(y2), "v"(y3));
         const global_bytes mid = pair_ptr + lane_bytes;
         if constexpr (decltype(second)::value)
@@ -1047,7 +1063,7 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
     // seeds' transcendental evaluation and the tables below, so that the period's first L2 round trip runs under the set-up -- measured 7.60 against 7.54 us per period:
     // the other waves of the unit already cover that latency, and the eight registers held through the set-up cost more.)
     constexpr bool EARLY_LOADS = GSH_MC_EARLY_LOADS && MRG && MC_THREADS > 256;
-    float4 qa[PF], qb[PF];
+    float4 qa[NQ], qb[NQ];
     auto first_loads = [&]() {
 #pragma unroll
         for (int j = 0; j < PF; j++)
@@ -1228,13 +1244,14 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
     int until_reseed = 0, r_idx = 0, tbl0 = 0;
     using std::integral_constant;
     // one trip; j: its slot in the load queue; FA / FB (compile time): chunk A / B reads its early tap next to the late one
-    // (pm, optional: 1 / 2 -- the first / second trip of a pair, see PAIRS: both issue plain loads off pair_ptr, and the second never re-seeds -- the caller vouches)
+    // (pm, optional: 1 / 2 -- the first / second trip of a pair, see PAIRS: both issue plain loads off pair_ptr, and the second never re-seeds -- the caller vouches;
+    //  3: a second trip that issues no loads, the last one of a run of pairs with two trips of loads in flight)
     auto trip = [&](int i, auto jc, auto fa, auto fb, auto kp, auto... pm) {
         constexpr int PM = (0 + ... + decltype(pm)::value);
         constexpr int j = decltype(jc)::value;
         constexpr bool FA = decltype(fa)::value, FB = decltype(fb)::value;
         constexpr bool KP = decltype(kp)::value;  // the caller knows that trip i is a plain one (first_plain <= i < last_plain)
-        if (PM != 2 && until_reseed == 0)  // uniform: exact re-seed of the lane's phasor and of (float)n
+        if (PM < 2 && until_reseed == 0)  // uniform: exact re-seed of the lane's phasor and of (float)n
             {
                 const int n0 = lane_n0(i);
                 if (!single && !fac && r_idx - tbl0 >= TBL)
@@ -1306,7 +1323,9 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
                     }
             }
 #if GSH_MC_RUNLEN
-        if constexpr (PM != 0)
+        if constexpr (PM == 3)
+            ;
+        else if constexpr (PM != 0)
             load_pair(integral_constant<bool, PM == 2>{}, qa[j], qb[j], yA0, yA1, yB0, yB1);
         else if constexpr ((FA && (FB || NCH == 1)) || KP)
             {
@@ -1394,21 +1413,50 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
                                     if (until_reseed & 1) np = min(np, until_reseed >> 1);
                                     if (np > 0)  // uniform
                                         {
-                                            pair_ptr = trip_base(i + 1, 24 * PPC);
                                             run -= 2 * np;
-                                            do
+                                            if constexpr (QUEUE2)
                                                 {
+                                                    // both trips of a pass issue the loads of the trip two ahead of them, trips i + 2 and i + 3, around one running base.  The pass
+                                                    // before the last one so issues the loads of the last pass' two trips, which lie in the run; the last pass issues those of the trip
+                                                    // behind the run alone (a plain one: np above).  No load goes out that the one-deep queue does not issue.
+                                                    using j1 = integral_constant<int, 1>;
+                                                    pair_ptr = trip_base(i + 2, 24 * PPC);
+                                                    load_plain(i + 1, qa[j1::value], qb[j1::value]);
+                                                    while (--np > 0)
+                                                        {
+                                                            trip(i, j0{}, yes{}, yes{}, no{}, integral_constant<int, 1>{});
+#if GSH_MC_PAIR_BARRIER
+                                                            __builtin_amdgcn_sched_barrier(0);
+#endif
+                                                            trip(i + 1, j1{}, yes{}, yes{}, no{}, integral_constant<int, 2>{});
+                                                            i += 2;
+                                                            pair_ptr += 2 * TRIP * static_cast<int>(sizeof(float2));
+                                                            asm("" : "+s"(pair_ptr));
+                                                        }
                                                     trip(i, j0{}, yes{}, yes{}, no{}, integral_constant<int, 1>{});
-                                                    // (the two trips one after the other: left to interleave them the scheduler starts the second trip's chains under the
-                                                    //  first one's accumulates and the kernel needs 90 VGPRs instead of 82 -- ISA, round 9)
+#if GSH_MC_PAIR_BARRIER
                                                     __builtin_amdgcn_sched_barrier(0);
-                                                    trip(i + 1, j0{}, yes{}, yes{}, no{}, integral_constant<int, 2>{});
+#endif
+                                                    trip(i + 1, j1{}, yes{}, yes{}, no{}, integral_constant<int, 3>{});
                                                     i += 2;
-                                                    pair_ptr += 2 * TRIP * static_cast<int>(sizeof(float2));
-                                                    asm("" : "+s"(pair_ptr));
-                                                    np--;
                                                 }
-                                            while (np > 0);
+                                            else
+                                                {
+                                                    pair_ptr = trip_base(i + 1, 24 * PPC);
+                                                    do
+                                                        {
+                                                            trip(i, j0{}, yes{}, yes{}, no{}, integral_constant<int, 1>{});
+                                                            // (the two trips one after the other: left to interleave them the scheduler starts the second trip's chains under the
+                                                            //  first one's accumulates and the kernel needs 90 VGPRs instead of 82 -- ISA, round 9)
+                                                            __builtin_amdgcn_sched_barrier(0);
+                                                            trip(i + 1, j0{}, yes{}, yes{}, no{}, integral_constant<int, 2>{});
+                                                            i += 2;
+                                                            pair_ptr += 2 * TRIP * static_cast<int>(sizeof(float2));
+                                                            asm("" : "+s"(pair_ptr));
+                                                            np--;
+                                                        }
+                                                    while (np > 0);
+                                                }
                                             if (run == 0) run = paired_run(i);  // uniform
                                             continue;
                                         }
