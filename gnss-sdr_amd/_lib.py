@@ -187,6 +187,28 @@ class CondConf(C.Structure):
     ]
 
 
+class CondBlanking(C.Structure):
+    """gsh_cond_blanking (16 bytes): the conditioner's pulse-blanking stage."""
+    _fields_ = [
+        ("pfa", C.c_float),
+        ("length", C.c_int32),
+        ("n_segments_est", C.c_int32),
+        ("n_segments_reset", C.c_int32),
+    ]
+
+
+class CondBlankingState(C.Structure):
+    """struct gsh_cond_blanking_state (32 bytes)."""
+    _fields_ = [
+        ("thres", C.c_float),
+        ("noise_power_estimation", C.c_float),
+        ("n_segments", C.c_int32),
+        ("last_filtered", C.c_int32),
+        ("n_decided", C.c_uint64),
+        ("n_blanked", C.c_uint64),
+    ]
+
+
 class AcqResult(C.Structure):
     """gsh_acq_result."""
     _fields_ = [
@@ -325,6 +347,9 @@ SYMBOLS = {
     "gsh_cond_push_pinned_async": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsh_cond_position": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsh_cond_time_push": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _F]),
+    "gsh_cond_set_blanking": (C.c_int, [_P, C.POINTER(CondBlanking)]),
+    "gsh_cond_plan_blanked": (C.c_int, [C.POINTER(CondConf), C.POINTER(CondBlanking), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gsh_cond_blanking_state": (C.c_int, [_P, C.POINTER(CondBlankingState)]),
     "gsh_gen_create": (C.c_int, [C.c_int, C.c_double, C.c_int32, C.POINTER(_P)]),
     "gsh_gen_destroy": (None, [_P]),
     "gsh_gen_set_satellite": (C.c_int, [_P, C.c_int32, _F, _F, C.c_uint32, C.c_uint32, _I8, C.c_int32, _I8, C.c_int32, C.c_double, C.c_double, C.c_double]),

@@ -44,30 +44,58 @@ def _conf(input_kind, inverted_spectrum, taps, decimation, center_freq_hz, sampl
     return c, t
 
 
+BLANKING_DEFAULTS = dict(pfa=0.04, length=32, segments_est=12500, segments_reset=5000000)   # pulse_blanking_filter.cc:43-50
+
+
+def _blanking(blanking):
+    """None or the property names of Pulse_Blanking_Filter (pfa, length, segments_est, segments_reset; defaults of the reference) -> gsh_cond_blanking"""
+    if blanking is None:
+        return None
+    unknown = set(blanking) - set(BLANKING_DEFAULTS)
+    if unknown:
+        raise ValueError(f"blanking: unknown keys {sorted(unknown)} (known: {', '.join(BLANKING_DEFAULTS)})")
+    b = dict(BLANKING_DEFAULTS, **blanking)
+    return _lib.CondBlanking(float(b["pfa"]), int(b["length"]), int(b["segments_est"]), int(b["segments_reset"]))
+
+
 def outputs_after(n_in_total: int, input_kind="gr_complex", inverted_spectrum: bool = False, taps=None, decimation: int = 1, center_freq_hz: float = 0.0,
-                  sampling_freq_hz: float = 1.0, fs_in: float = 0.0, fs_out: float = 0.0) -> int:
-    """gsh_cond_plan: ring samples such a conditioner has produced once n_in_total input samples have arrived.  Host arithmetic, no GPU."""
+                  sampling_freq_hz: float = 1.0, fs_in: float = 0.0, fs_out: float = 0.0, blanking=None) -> int:
+    """gsh_cond_plan / gsh_cond_plan_blanked: ring samples such a conditioner has produced once n_in_total input samples have arrived.  Host
+    arithmetic, no GPU."""
     c, _t = _conf(input_kind, inverted_spectrum, taps, decimation, center_freq_hz, sampling_freq_hz, fs_in, fs_out)
     out = C.c_uint64(0)
-    check(_lib.load().gsh_cond_plan(C.byref(c), int(n_in_total), C.byref(out)))
+    b = _blanking(blanking)
+    if b is None:
+        check(_lib.load().gsh_cond_plan(C.byref(c), int(n_in_total), C.byref(out)))
+    else:
+        check(_lib.load().gsh_cond_plan_blanked(C.byref(c), C.byref(b), int(n_in_total), C.byref(out)))
     return int(out.value)
 
 
 class SignalConditioner:
     """One handle for the whole chain.  input_kind: "gr_complex" / "ishort" / "ibyte" (complex items), "float" / "short" / "byte" (real items: they
     need a filter) or a PackedFormat.  taps None or empty: no filter.  fs_in = fs_out = 0: no resampler (fs_in is the rate after the filter).
+    blanking: None, or dict(pfa=0.04, length=32, segments_est=12500, segments_reset=5000000) (any subset): pulse blanking (Pulse_Blanking_Filter)
+    between the filter and the resampler; whole segments of `length` filter outputs are emitted, a partial one waits for the next push.
     Every push returns (first_out, n_out): the ring index of the block's first output and how many outputs it completed."""
 
     def __init__(self, ring: SampleStream | None = None, input_kind="gr_complex", inverted_spectrum: bool = False, taps=None, decimation: int = 1,
-                 center_freq_hz: float = 0.0, sampling_freq_hz: float = 1.0, fs_in: float = 0.0, fs_out: float = 0.0, device: int = 0):
+                 center_freq_hz: float = 0.0, sampling_freq_hz: float = 1.0, fs_in: float = 0.0, fs_out: float = 0.0, device: int = 0, blanking=None):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.input_kind = input_kind
         c, _t = _conf(input_kind, inverted_spectrum, taps, decimation, center_freq_hz, sampling_freq_hz, fs_in, fs_out)
         self._np = None if c.input == INPUT_PACKED else _REAL_NP[c.item_type] if c.input == INPUT_REAL else _ITEM_NP[c.item_type]
         self._per_sample = 1 if c.input != INPUT_ITEMS or c.item_type == 0 else 2   # array elements per input sample
+        b = _blanking(blanking)
         check(self._lib.gsh_cond_create(device, C.byref(c), C.byref(self._h)))
         self.ring = None
+        if b is not None:
+            try:
+                check(self._lib.gsh_cond_set_blanking(self._h, C.byref(b)))
+            except Exception:
+                self.close()
+                raise
         if ring is not None:
             self.bind(ring)
 
@@ -79,8 +107,8 @@ class SignalConditioner:
           InputFilter      Pass_Through | Fir_Filter | Freq_Xlating_Fir_Filter with input_item_type, decimation_factor, IF, sampling_frequency
                            (freq_xlating_fir_filter.cc:62-75) and `taps`: the caller's (firdes_low_pass, or a Remez design made on the host)
           Resampler        Pass_Through | Direct_Resampler with sample_freq_in, sample_freq_out (direct_resampler_conditioner.cc:36-43)
-        ValueError for an implementation the one-pass conditioner does not cover (Pulse_Blanking_Filter, Notch_Filter, Notch_Filter_Lite stay loose
-        calls: PulseBlanking, NotchFilter)."""
+        ValueError for an implementation this mapping does not cover: Notch_Filter, Notch_Filter_Lite stay loose calls (NotchFilter), and
+        Pulse_Blanking_Filter is mapped by properties_with_mitigation()."""
         ada, fil, res = (dict(role.get(k, {})) for k in ("DataTypeAdapter", "InputFilter", "Resampler"))
         a_impl, f_impl, r_impl = (d.get("implementation", "Pass_Through") for d in (ada, fil, res))
         if a_impl not in ADAPTERS:
@@ -114,6 +142,48 @@ class SignalConditioner:
     @classmethod
     def from_properties(cls, ring: SampleStream | None, role: dict, device: int = 0) -> "SignalConditioner":
         return cls(ring, device=device, **cls.properties(role))
+
+    @staticmethod
+    def properties_with_mitigation(role: dict) -> dict:
+        """properties() with InputFilter.implementation=Pulse_Blanking_Filter covered as well (pulse_blanking_filter.cc:43-53, :73-84):
+          pfa, length, segments_est, segments_reset   the `blanking` keyword (defaults 0.04, 32, 12500, 5000000)
+          IF (or `if`), sampling_frequency            |IF| > 1: a Freq_Xlating_Fir_Filter with decimation 1 in front of the blanker; its `taps` are
+                                                      the caller's (the reference designs firdes::low_pass(1, sampling_frequency, bw, tw)).  |IF| <= 1: no filter
+          item_type                                   gr_complex only
+        Every other implementation is delegated to properties()."""
+        fil = dict(role.get("InputFilter", {}))
+        if fil.get("implementation", "Pass_Through") != "Pulse_Blanking_Filter":
+            return SignalConditioner.properties(role)
+        if fil.get("item_type", "gr_complex") != "gr_complex":
+            raise ValueError(f"InputFilter.item_type {fil['item_type']!r}: Pulse_Blanking_Filter takes gr_complex only")
+        kw = SignalConditioner.properties({k: v for k, v in role.items() if k != "InputFilter"})
+        if kw["input_kind"] not in ("gr_complex", "ibyte", "ishort"):
+            raise ValueError(f"Pulse_Blanking_Filter takes gr_complex, the adapter yields {kw['input_kind']!r}")
+        if_hz = float(fil.get("IF", fil.get("if", 0.0)))
+        if abs(if_hz) > 1.0:
+            if "taps" not in fil:
+                raise ValueError("InputFilter.taps: |IF| > 1 puts a Freq_Xlating_Fir_Filter in front of the blanker; its taps are the caller's "
+                                 "(firdes_low_pass(1, sampling_frequency, bw, tw))")
+            kw.update(taps=fil["taps"], decimation=1, center_freq_hz=if_hz, sampling_freq_hz=float(fil.get("sampling_frequency", 4000000.0)))
+        kw["blanking"] = {k: type(d)(fil.get(k, d)) for k, d in BLANKING_DEFAULTS.items()}
+        return kw
+
+    @classmethod
+    def from_properties_with_mitigation(cls, ring: SampleStream | None, role: dict, device: int = 0) -> "SignalConditioner":
+        return cls(ring, device=device, **cls.properties_with_mitigation(role))
+
+    def set_blanking(self, blanking) -> None:
+        """gsh_cond_set_blanking: before the first push only; None turns the stage off"""
+        b = _blanking(blanking)
+        check(self._lib.gsh_cond_set_blanking(self._h, C.byref(b) if b is not None else None))
+
+    def blanking_state(self) -> dict:
+        """gsh_cond_blanking_state (waits for the queued pushes): thres, noise_power_estimation, n_segments, last_filtered, and the counters
+        n_decided / n_blanked -- the duty cycle of the blanker"""
+        s = _lib.CondBlankingState()
+        check(self._lib.gsh_cond_blanking_state(self._h, C.byref(s)))
+        return dict(thres=np.float32(s.thres), noise_power_estimation=np.float32(s.noise_power_estimation), n_segments=int(s.n_segments),
+                    last_filtered=bool(s.last_filtered), n_decided=int(s.n_decided), n_blanked=int(s.n_blanked))
 
     def close(self):
         if self._h:

@@ -52,6 +52,43 @@ struct CondArgs
     PackedCode packed;           // kind COND_PACKED
 };
 
+// filter output that feeds output d of the launch: resample_gather_kernel's index (resampler.hip), d below 2^32
+__device__ __forceinline__ unsigned long long cond_filter_index(const CondArgs& a, unsigned long long d)
+{
+    if (a.rs_mode == COND_RS_DECIMATE) return a.q0 + (a.r0 + (d << 32)) / a.step;
+    if (a.rs_mode == COND_RS_INTERPOLATE) return a.q0 + ((a.r0 + d * a.step) >> 32);
+    return a.out0 + d;
+}
+
+// ---- the blanking stage (cond_blanking.hip): pulse_blanking_cc between the filter and the resampler.  A push forms its new filter outputs behind
+// the carry of the open segment in a stage buffer (cond_launch without a resampler), then: one energy per completed segment, the decision over
+// them, and the masked gather into the ring.
+struct CondBlankState          // device memory, carried from push to push
+{
+    float noise_power_estimation;
+    int n_segments;
+    int last_filtered;
+    int reserved;
+    unsigned long long n_decided, n_blanked;  // segments decided since the handle was created, and those of them that were blanked
+};
+struct CondBlankArgs
+{
+    const float2* stage;       // filter outputs base, base + 1, ...: the carry, then the push's new ones
+    float* energy;             // n_seg
+    unsigned char* mask;       // n_seg
+    const CondBlankState* state_in;
+    CondBlankState* state_out; // (gsh_cond_time_push: a copy)
+    unsigned long long base;   // absolute filter-output index of stage[0]: a multiple of length
+    unsigned long long n_seg;  // segments this push completes: stage[0 .. n_seg * length)
+    int length, n_segments_est, n_segments_reset;
+    float thres;
+};
+// queue the energies and the decision of b.n_seg > 0 segments
+int cond_blank_launch_decide(const CondBlankArgs& b, hipStream_t st);
+// queue the gather: ring samples [a.out0, a.out0 + a.n_out) into a.out, each mask ? 0 : stage[m(j) - base] (a: q0, r0 planned; every m(j) within
+// the decided segments)
+int cond_blank_launch_gather(const CondArgs& a, const CondBlankArgs& b, hipStream_t st);
+
 // q0, r0 of a launch whose first output is a.out0 (a.step, a.rs_mode set)
 void cond_plan_resampler(CondArgs* a);
 // a.tile, a.max_span for the handle's filter and ratio: the largest power of two of outputs whose inputs fit COND_MAX_SPAN

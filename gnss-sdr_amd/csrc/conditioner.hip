@@ -10,7 +10,13 @@
 // -- a function of N alone, so the ring's content does not depend on where the stream is cut.  The first output of a push has m(j) >= M of the
 // stream before it, so it reaches back K - 1 input samples at most: that is the history the handle keeps (an interpolating resampler that takes
 // a filter output twice takes it twice in the same push).
+//
+// With the blanking stage (gsh_cond_set_blanking; kernels in cond_blanking.hip) the resampler sees whole segments only: M' = floor(M / L) L in place
+// of M above.  A push forms every new filter output behind the carry of the open segment (at most L - 1 outputs, kept in device memory,
+// double-buffered and ordered by the same event as the history) in the handle's stage buffer, decides the segments these complete on the device, and
+// gathers mask ? 0 : stage[m(j) - base] into the ring; the state never comes back to the host.
 #include "conditioner.h"
+#include "pulse_blanking.h"
 #include "resample_index.h"
 #include "sample_convert.h"
 #include "sample_stream.h"
@@ -92,15 +98,40 @@ int reduce_conf(const gsh_cond_conf* conf, CondPlan* p)
     return GSH_OK;
 }
 
-// ring samples produced once n_in input samples have arrived (see the head of the file)
-unsigned long long outputs_after(const CondPlan& p, unsigned long long n_in)
+// filter outputs complete once n_in input samples have arrived
+unsigned long long filter_outputs_after(const CondPlan& p, unsigned long long n_in)
 {
     const unsigned long long D = static_cast<unsigned long long>(p.decimation);
-    const unsigned long long M = (n_in + D - 1) / D;
+    return (n_in + D - 1) / D;
+}
+
+// ring samples produced once n_in input samples have arrived (see the head of the file); length > 0: with the blanking stage, which hands the
+// resampler whole segments only
+unsigned long long outputs_after(const CondPlan& p, unsigned long long n_in, int length = 0)
+{
+    unsigned long long M = filter_outputs_after(p, n_in);
+    if (length > 0) M -= M % static_cast<unsigned long long>(length);
     if (M == 0 || p.rs_mode == gsh::COND_RS_NONE) return M;
     if (p.rs_mode == gsh::COND_RS_DECIMATE) return static_cast<unsigned long long>((static_cast<unsigned __int128>(M - 1) * p.step) >> 32) + 1;
     return static_cast<unsigned long long>(((static_cast<unsigned __int128>(M) << 32) + p.step - 1) / p.step) - 1;
 }
+
+// gsh_pb_create's ranges
+int check_blanking(const gsh_cond_blanking* b)
+{
+    GSH_REQUIRE(b->pfa > 0.0f && b->pfa < 1.0f, "pfa %g outside (0, 1)", static_cast<double>(b->pfa));
+    GSH_REQUIRE(b->length >= 1 && b->length <= gsh::PB_MAX_LENGTH, "length %d outside 1..%d", b->length, gsh::PB_MAX_LENGTH);
+    GSH_REQUIRE(b->n_segments_est >= 0 && b->n_segments_reset >= 0, "negative segment count");
+    return GSH_OK;
+}
+
+// what a push of n_in samples does to the segments: stage[0] is filter output `base`, the first of the open segment
+struct BlankFrame
+{
+    unsigned long long M0, base, c0;  // filter outputs before the push, the mitigated ones of them, the carry M0 - base
+    unsigned long long n_new;         // filter outputs the push completes
+    unsigned long long n_seg, c1;     // segments it completes, and the carry it leaves
+};
 }  // namespace
 
 struct gsh_cond
@@ -124,6 +155,20 @@ struct gsh_cond
     size_t stage_cap[COND_NSTAGE]{};
     hipEvent_t stage_done[COND_NSTAGE]{};  // the launch that read d_stage[i] has finished
     int stage_next{0};
+    // the blanking stage (gsh_cond_set_blanking)
+    bool blank_on{false};
+    gsh_cond_blanking blank{};
+    float thres{0.0f};
+    gsh::CondBlankState* d_bstate{nullptr};   // [0] the state, [1] the copy gsh_cond_time_push writes
+    float2* d_carry[2]{nullptr, nullptr};     // the open segment's filter outputs, double-buffered like the history (ordered by hist_ev too)
+    int carry_cur{0};
+    int stage_tile{0}, stage_span{0};         // cond_tile() of the launch that forms every filter output
+    void* d_y{nullptr};                       // stage buffer: the carry, then the push's filter outputs
+    size_t y_cap{0};
+    void* d_energy{nullptr};
+    size_t energy_cap{0};
+    void* d_mask{nullptr};
+    size_t mask_cap{0};
 };
 
 namespace
@@ -144,7 +189,9 @@ int check_push(const gsh_cond* h, const void* items, unsigned long long n_in, un
     GSH_REQUIRE(h->ring != nullptr, "no ring bound (gsh_cond_bind)");
     int rc = block_bytes(h, n_in, bytes);
     if (rc != GSH_OK) return rc;
-    *count = outputs_after(h->plan, h->n_in_total + n_in) - h->n_out_total;
+    *count = outputs_after(h->plan, h->n_in_total + n_in, h->blank_on ? h->blank.length : 0) - h->n_out_total;
+    if (h->blank_on)
+        GSH_REQUIRE(filter_outputs_after(h->plan, n_in) + static_cast<unsigned long long>(h->blank.length) < (1ull << 32), "more than 2^32 filter outputs in one push");
     gsh_stream* ring = h->ring;
     rc = gsh::stream_multi_check_rings(&ring, 1, *count);
     if (rc != GSH_OK) return rc;
@@ -185,9 +232,107 @@ int write_segment(void* ctx, unsigned long long first, unsigned long long len, f
     return gsh::cond_launch(a, st);
 }
 
+int grow(void** buf, size_t* cap, size_t bytes)
+{
+    if (bytes <= *cap) return GSH_OK;
+    if (*buf) GSH_HIP(hipFree(*buf));  // (hipFree waits for the device: nothing still reads the old buffer)
+    *buf = nullptr;
+    *cap = 0;
+    GSH_HIP(hipMalloc(buf, bytes + bytes / 2));
+    *cap = bytes + bytes / 2;
+    return GSH_OK;
+}
+
+BlankFrame blank_frame(const gsh_cond* h, unsigned long long n_in)
+{
+    const unsigned long long L = static_cast<unsigned long long>(h->blank.length);
+    BlankFrame f;
+    f.M0 = filter_outputs_after(h->plan, h->n_in_total);
+    const unsigned long long M1 = filter_outputs_after(h->plan, h->n_in_total + n_in);
+    f.base = f.M0 - f.M0 % L;
+    f.c0 = f.M0 - f.base;
+    f.n_new = M1 - f.M0;
+    f.n_seg = (M1 - f.base) / L;
+    f.c1 = M1 - f.base - f.n_seg * L;
+    return f;
+}
+
+// the handle's buffers for a frame, before anything is queued
+int blank_reserve(gsh_cond* h, const BlankFrame& f)
+{
+    int rc = grow(&h->d_y, &h->y_cap, sizeof(float2) * (f.c0 + f.n_new));
+    if (rc == GSH_OK) rc = grow(&h->d_energy, &h->energy_cap, sizeof(float) * f.n_seg);
+    if (rc == GSH_OK) rc = grow(&h->d_mask, &h->mask_cap, f.n_seg);
+    return rc;
+}
+
+// queue the carry, the push's filter outputs behind it, the energies and the decision of the segments they complete, and the carry the push leaves
+// in the other half; *b = what the gather needs
+int blank_stage(const gsh_cond* h, const CondArgs& block, const BlankFrame& f, gsh::CondBlankState* state_out, hipStream_t st, gsh::CondBlankArgs* b)
+{
+    float2* y = static_cast<float2*>(h->d_y);
+    if (f.c0 > 0) GSH_HIP(hipMemcpyAsync(y, h->d_carry[h->carry_cur], sizeof(float2) * f.c0, hipMemcpyDeviceToDevice, st));
+    if (f.n_new > 0)
+        {
+            CondArgs a = block;  // every filter output: the chain's launch without its resampler
+            a.rs_mode = gsh::COND_RS_NONE;
+            a.step = 0u;
+            a.q0 = a.r0 = 0;
+            a.tile = h->stage_tile;
+            a.max_span = h->stage_span;
+            a.out = y + f.c0;
+            a.out0 = f.M0;
+            a.n_out = f.n_new;
+            int rc = gsh::cond_launch(a, st);
+            if (rc != GSH_OK) return rc;
+        }
+    b->stage = y;
+    b->energy = static_cast<float*>(h->d_energy);
+    b->mask = static_cast<unsigned char*>(h->d_mask);
+    b->state_in = h->d_bstate;
+    b->state_out = state_out;
+    b->base = f.base;
+    b->n_seg = f.n_seg;
+    b->length = h->blank.length;
+    b->n_segments_est = h->blank.n_segments_est;
+    b->n_segments_reset = h->blank.n_segments_reset;
+    b->thres = h->thres;
+    if (f.n_seg > 0)
+        {
+            int rc = gsh::cond_blank_launch_decide(*b, st);
+            if (rc != GSH_OK) return rc;
+        }
+    if (f.c1 > 0)
+        GSH_HIP(hipMemcpyAsync(h->d_carry[h->carry_cur ^ 1], y + f.n_seg * static_cast<unsigned long long>(h->blank.length), sizeof(float2) * f.c1,
+            hipMemcpyDeviceToDevice, st));
+    return GSH_OK;
+}
+
+struct BlankSegmentCtx
+{
+    CondArgs a;
+    unsigned long long out0;
+    gsh::CondBlankArgs b;
+};
+
+// MultiSegmentWriter of a push with the blanking stage
+int write_segment_blanked(void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t st)
+{
+    const BlankSegmentCtx* c = static_cast<const BlankSegmentCtx*>(ctx);
+    CondArgs a = c->a;
+    a.out = dst[0];
+    a.out0 = c->out0 + first;
+    a.n_out = len;
+    gsh::cond_plan_resampler(&a);
+    return gsh::cond_blank_launch_gather(a, c->b, st);
+}
+
+int push_block_blanked(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st);
+
 // queue the device work of a checked push on st and advance the handle
 int push_block(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st)
 {
+    if (h->blank_on) return push_block_blanked(h, d_block, n_in, count, st);
     if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
     SegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total};
     if (count > 0)
@@ -211,14 +356,34 @@ int push_block(gsh_cond* h, const void* d_block, unsigned long long n_in, unsign
     return GSH_OK;
 }
 
-int grow(void** buf, size_t* cap, size_t bytes)
+int push_block_blanked(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st)
 {
-    if (bytes <= *cap) return GSH_OK;
-    if (*buf) GSH_HIP(hipFree(*buf));  // (hipFree waits for the device: nothing still reads the old buffer)
-    *buf = nullptr;
-    *cap = 0;
-    GSH_HIP(hipMalloc(buf, bytes + bytes / 2));
-    *cap = bytes + bytes / 2;
+    const BlankFrame f = blank_frame(h, n_in);
+    int rc = blank_reserve(h, f);
+    if (rc != GSH_OK) return rc;
+    if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
+    BlankSegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total, {}};
+    rc = blank_stage(h, ctx.a, f, h->d_bstate, st, &ctx.b);
+    if (rc != GSH_OK) return rc;
+    if (count > 0)
+        {
+            rc = gsh::stream_write_device_multi(&h->ring, 1, count, st, write_segment_blanked, &ctx);
+            if (rc != GSH_OK) return rc;
+        }
+    if (n_in > 0)
+        {
+            if (h->plan.n_taps > 1)
+                {
+                    rc = gsh::cond_launch_history(ctx.a, st);
+                    if (rc != GSH_OK) return rc;
+                    h->cur ^= 1;
+                }
+            GSH_HIP(hipEventRecord(h->hist_ev, st));
+            h->hist_recorded = true;
+        }
+    if (f.c1 > 0) h->carry_cur ^= 1;
+    h->n_in_total += n_in;
+    h->n_out_total += count;
     return GSH_OK;
 }
 
@@ -239,6 +404,67 @@ extern "C"
         int rc = reduce_conf(conf, &p);
         if (rc != GSH_OK) return rc;
         *n_out_total = outputs_after(p, n_in_total);
+        return GSH_OK;
+    }
+
+    int gsh_cond_plan_blanked(const gsh_cond_conf* conf, const gsh_cond_blanking* blanking, uint64_t n_in_total, uint64_t* n_out_total)
+    {
+        if (blanking == nullptr) return gsh_cond_plan(conf, n_in_total, n_out_total);
+        GSH_REQUIRE(n_out_total != nullptr, "null n_out_total");
+        *n_out_total = 0;
+        CondPlan p;
+        int rc = reduce_conf(conf, &p);
+        if (rc == GSH_OK) rc = check_blanking(blanking);
+        if (rc != GSH_OK) return rc;
+        *n_out_total = outputs_after(p, n_in_total, blanking->length);
+        return GSH_OK;
+    }
+
+    int gsh_cond_set_blanking(gsh_cond_t* h, const gsh_cond_blanking* blanking)
+    {
+        GSH_REQUIRE(h != nullptr, "null conditioner");
+        if (h->n_in_total != 0 || h->hist_recorded) return set_error(GSH_ERR_STATE, "the blanking stage is set before the handle's first push (%llu samples taken)", h->n_in_total);
+        if (blanking == nullptr)
+            {
+                h->blank_on = false;
+                return GSH_OK;
+            }
+        int rc = check_blanking(blanking);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipSetDevice(h->device));
+        h->blank_on = false;
+        if (h->d_bstate == nullptr) GSH_HIP(hipMalloc(&h->d_bstate, 2 * sizeof(gsh::CondBlankState)));
+        GSH_HIP(hipMemset(h->d_bstate, 0, 2 * sizeof(gsh::CondBlankState)));  // pulse_blanking_cc.cc:38-44
+        if (h->d_carry[0]) GSH_HIP(hipFree(h->d_carry[0]));
+        h->d_carry[0] = h->d_carry[1] = nullptr;
+        GSH_HIP(hipMalloc(&h->d_carry[0], sizeof(float2) * 2 * static_cast<size_t>(blanking->length)));
+        h->d_carry[1] = h->d_carry[0] + blanking->length;
+        h->carry_cur = 0;
+        CondArgs a = h->base;
+        a.rs_mode = gsh::COND_RS_NONE;
+        gsh::cond_tile(&a);
+        h->stage_tile = a.tile;
+        h->stage_span = a.max_span;
+        h->blank = *blanking;
+        h->thres = gsh::pb_threshold(blanking->pfa, blanking->length);
+        h->blank_on = true;
+        return GSH_OK;
+    }
+
+    int gsh_cond_blanking_state(gsh_cond_t* h, struct gsh_cond_blanking_state* state)
+    {
+        GSH_REQUIRE(h != nullptr && state != nullptr, "null argument");
+        if (!h->blank_on) return set_error(GSH_ERR_STATE, "the conditioner has no blanking stage (gsh_cond_set_blanking)");
+        GSH_HIP(hipSetDevice(h->device));
+        if (h->hist_recorded) GSH_HIP(hipEventSynchronize(h->hist_ev));
+        gsh::CondBlankState s{};
+        GSH_HIP(hipMemcpy(&s, h->d_bstate, sizeof(s), hipMemcpyDeviceToHost));
+        state->thres = h->thres;
+        state->noise_power_estimation = s.noise_power_estimation;
+        state->n_segments = s.n_segments;
+        state->last_filtered = s.last_filtered;
+        state->n_decided = s.n_decided;
+        state->n_blanked = s.n_blanked;
         return GSH_OK;
     }
 
@@ -298,6 +524,11 @@ extern "C"
         if (h->d_taps) (void)hipFree(h->d_taps);
         if (h->d_hist[0]) (void)hipFree(h->d_hist[0]);
         if (h->d_raw) (void)hipFree(h->d_raw);
+        if (h->d_bstate) (void)hipFree(h->d_bstate);
+        if (h->d_carry[0]) (void)hipFree(h->d_carry[0]);
+        if (h->d_y) (void)hipFree(h->d_y);
+        if (h->d_energy) (void)hipFree(h->d_energy);
+        if (h->d_mask) (void)hipFree(h->d_mask);
         for (int i = 0; i < COND_NSTAGE; i++)
             {
                 if (h->d_stage[i]) (void)hipFree(h->d_stage[i]);
@@ -397,10 +628,19 @@ extern "C"
         unsigned long long bytes = 0;
         int rc = block_bytes(h, n_in, &bytes);
         if (rc != GSH_OK) return rc;
-        const unsigned long long count = outputs_after(h->plan, h->n_in_total + n_in) - h->n_out_total;
+        const unsigned long long count = outputs_after(h->plan, h->n_in_total + n_in, h->blank_on ? h->blank.length : 0) - h->n_out_total;
         GSH_REQUIRE(count >= 1 && count < (1ull << 32), "a block of %llu samples completes %llu outputs: nothing to time", static_cast<unsigned long long>(n_in), count);
         GSH_HIP(hipSetDevice(h->device));
-        // the launches of a push, into a scratch destination instead of the ring; the history update lands in the half no push has flipped to
+        // the launches of a push, into a scratch destination instead of the ring; the history update lands in the half no push has flipped to (with
+        // the blanking stage: so does the carry, and the decision writes the copy of the state)
+        BlankFrame f{};
+        if (h->blank_on)
+            {
+                GSH_REQUIRE(filter_outputs_after(h->plan, n_in) + static_cast<unsigned long long>(h->blank.length) < (1ull << 32), "more than 2^32 filter outputs in one push");
+                f = blank_frame(h, n_in);
+                rc = blank_reserve(h, f);
+                if (rc != GSH_OK) return rc;
+            }
         float2* d_out = nullptr;
         GSH_HIP(hipMalloc(&d_out, sizeof(float2) * count));
         CondArgs a = block_args(h, device_block, n_in);
@@ -412,7 +652,15 @@ extern "C"
         hipError_t e = hipSuccess;
         if (h->hist_recorded && (e = hipStreamWaitEvent(st, h->hist_ev, 0)) != hipSuccess) rc = gsh::hip_fail(e, "hipStreamWaitEvent", __FILE__, __LINE__);
         auto once = [&]() {
-            int r = gsh::cond_launch(a, st);
+            int r = GSH_OK;
+            if (h->blank_on)
+                {
+                    gsh::CondBlankArgs b{};
+                    r = blank_stage(h, a, f, h->d_bstate + 1, st, &b);
+                    if (r == GSH_OK) r = gsh::cond_blank_launch_gather(a, b, st);
+                }
+            else
+                r = gsh::cond_launch(a, st);
             if (r == GSH_OK && h->plan.n_taps > 1) r = gsh::cond_launch_history(a, st);
             return r;
         };

@@ -222,14 +222,6 @@ __device__ __forceinline__ float2 cond_translated(const CondArgs& a, long long n
     return fetch_translated<false>(t, n);
 }
 
-// filter output that feeds output d of the launch: resample_gather_kernel's index (resampler.hip), d below 2^32
-__device__ __forceinline__ unsigned long long cond_filter_index(const CondArgs& a, unsigned long long d)
-{
-    if (a.rs_mode == COND_RS_DECIMATE) return a.q0 + (a.r0 + (d << 32)) / a.step;
-    if (a.rs_mode == COND_RS_INTERPOLATE) return a.q0 + ((a.r0 + d * a.step) >> 32);
-    return a.out0 + d;
-}
-
 // A work-group stages the translated inputs of its tile of ring samples once -- from filter output m_first = m(tile0) to m_last = m(tile0 + cnt - 1),
 // (m_last - m_first) D + K samples -- and forms only the filter outputs the resampler keeps, each with fir_kernel's ascending-k fmaf chain.
 __global__ __launch_bounds__(FIR_THREADS) void cond_fir_kernel(CondArgs a)

@@ -11,7 +11,7 @@
 // Three launches per call: segment energies (data parallel), the state machine over the segments (one thread: it is the reference's
 // sequential recurrence, ~20 operations per segment), and the masked copy (data parallel).  Energies are sums of the float |x|^2 the
 // reference forms, added in double (its float VOLK accumulator has no defined lane order).  HBM-bound: 8 B read twice + 8 B written per sample.
-#include "gsh_internal.h"
+#include "pulse_blanking.h"
 #include <cmath>
 #include <new>
 
@@ -40,8 +40,6 @@ namespace gsh
 {
 namespace
 {
-constexpr int PB_THREADS = 256;
-
 // one thread per segment would read with a stride of `length` samples; instead a work-group stages a tile of |x|^2 in LDS with
 // coalesced reads and every thread then sums one segment out of LDS
 __global__ __launch_bounds__(PB_THREADS) void pb_energy_kernel(const float2* __restrict__ x, int length, unsigned long long n_seg, float* __restrict__ energy,
@@ -55,19 +53,14 @@ __global__ __launch_bounds__(PB_THREADS) void pb_energy_kernel(const float2* __r
     for (unsigned long long i = threadIdx.x; i < count; i += PB_THREADS)
         {
             const float2 v = x[base + i];
-            tile[i] = __fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y));  // volk_32fc_magnitude_squared_32f, :63
+            tile[i] = pb_mag2(v);
         }
     __syncthreads();
     for (unsigned long long s = threadIdx.x; s < segs; s += PB_THREADS)
-        {
-            double e = 0.0;
-            const float* t = tile + s * length;
-            for (int k = 0; k < length; k++) e += static_cast<double>(t[(k + static_cast<int>(s)) % length]);  // rotated start: spreads the LDS banks
-            energy[seg0 + s] = static_cast<float>(e);
-        }
+        energy[seg0 + s] = pb_segment_energy(tile + s * length, length, static_cast<int>(s));
 }
 
-// pulse_blanking_cc.cc:69-95, one segment after the other
+// pulse_blanking_cc.cc:69-95 (pb_decide_segments), one segment after the other
 __global__ void pb_decide_kernel(const float* __restrict__ energy, unsigned long long n_seg, unsigned char* __restrict__ mask, gsh_pulse_blanking::State* st,
     int n_segments_est, int n_segments_reset, float thres)
 {
@@ -76,30 +69,7 @@ __global__ void pb_decide_kernel(const float* __restrict__ energy, unsigned long
     int n_segments = st->n_segments;
     bool last_filtered = st->last_filtered != 0;
     const float n_deg = static_cast<float>(st->n_deg_fred);
-    for (unsigned long long s = 0; s < n_seg; s++)
-        {
-            const float segment_energy = energy[s];
-            unsigned char blank = 0;
-            if ((n_segments < n_segments_est) && (last_filtered == false))
-                {
-                    noise = __fdiv_rn(__fadd_rn(__fmul_rn(static_cast<float>(n_segments), noise), __fdiv_rn(segment_energy, n_deg)), static_cast<float>(n_segments + 1));
-                }
-            else
-                {
-                    if (__fdiv_rn(segment_energy, noise) > thres)
-                        {
-                            blank = 1;
-                            last_filtered = true;
-                        }
-                    else
-                        {
-                            last_filtered = false;
-                            if (n_segments > n_segments_reset) n_segments = 0;
-                        }
-                }
-            mask[s] = blank;
-            n_segments++;
-        }
+    pb_decide_segments(energy, n_seg, mask, noise, n_segments, last_filtered, n_deg, n_segments_est, n_segments_reset, thres, nullptr);
     st->noise_power_estimation = noise;
     st->n_segments = n_segments;
     st->last_filtered = last_filtered ? 1 : 0;
@@ -122,7 +92,7 @@ extern "C"
         GSH_REQUIRE(out != nullptr, "null argument");
         *out = nullptr;
         GSH_REQUIRE(pfa > 0.0f && pfa < 1.0f, "pfa %g outside (0, 1)", static_cast<double>(pfa));
-        GSH_REQUIRE(length >= 1 && length <= 4096, "length %d outside 1..4096", length);
+        GSH_REQUIRE(length >= 1 && length <= gsh::PB_MAX_LENGTH, "length %d outside 1..%d", length, gsh::PB_MAX_LENGTH);
         GSH_REQUIRE(n_segments_est >= 0 && n_segments_reset >= 0, "negative segment count");
         int rc = gsh::use_device(device);
         if (rc != GSH_OK) return rc;
@@ -132,8 +102,7 @@ extern "C"
         p->length = length;
         p->n_segments_est = n_segments_est;
         p->n_segments_reset = n_segments_reset;
-        // :48-49: thres_ = quantile(complement(chi_squared(2 * length), pfa)) = 2 * gamma_p_inv(length, 1 - pfa), in float
-        p->thres = static_cast<float>(2.0 * gsh::gamma_p_inv(static_cast<double>(length), 1.0 - static_cast<double>(pfa)));
+        p->thres = gsh::pb_threshold(pfa, length);
         auto fail = [&](hipError_t e, const char* what) {
             gsh::hip_fail(e, what, __FILE__, __LINE__);
             gsh_pb_destroy(p);
@@ -184,7 +153,7 @@ extern "C"
                 GSH_HIP(hipMalloc(&p->d_mask, n_seg));
                 p->seg_capacity = n_seg;
             }
-        const int seg_per_wg = std::max(1, 8192 / p->length);  // 32 KB of LDS per work-group
+        const int seg_per_wg = gsh::pb_seg_per_wg(p->length);
         const unsigned blocks_e = static_cast<unsigned>((n_seg + seg_per_wg - 1) / seg_per_wg);
         hipLaunchKernelGGL(gsh::pb_energy_kernel, dim3(blocks_e), dim3(gsh::PB_THREADS), sizeof(float) * static_cast<size_t>(seg_per_wg) * p->length, p->stream,
             static_cast<const float2*>(device_in_iq), p->length, static_cast<unsigned long long>(n_seg), p->d_energy, seg_per_wg);

@@ -552,8 +552,9 @@ extern "C"
      * / gsh_unpack_device -> gsh_fir_process_device -> gsh_direct_resample_device give for the concatenated input in one call per stage; where the
      * stream is cut into pushes does not matter.  Only the filter outputs the resampler keeps are formed.  The handle owns its device staging
      * and the converted history (n_taps - 1 samples) between pushes; all counts are integers computed on the host, a push reads nothing back.
-     * Not stages of this chain (they stay loose calls): Pulse_Blanking_Filter, Notch_Filter, Notch_Filter_Lite (gsh_pb_*, gsh_notch_*: sequential
-     * per-segment state); a fan-out of several filters into several rings; stream groups; the cshort / cbyte outputs of the xlating adapter
+     * Pulse_Blanking_Filter is an optional stage between the filter and the resampler (gsh_cond_set_blanking below).
+     * Not stages of this chain (they stay loose calls): Notch_Filter, Notch_Filter_Lite (gsh_notch_*: a one-sample advance and a state the host
+     * shadows); a fan-out of several filters into several rings; stream groups; the cshort / cbyte outputs of the xlating adapter
      * (freq_xlating_fir_filter.cc:136-160). */
 #define GSH_COND_INPUT_ITEMS 0  /* complex items of an enum gsh_item_type (item_type) */
 #define GSH_COND_INPUT_REAL 1   /* real items: item_type 1 float32, 2 int16, 3 int8 (the input_kind of gsh_fir_create); needs a filter */
@@ -602,6 +603,41 @@ extern "C"
     /* average HIP-event time of the device work of one push of device_block (n_in samples, device memory) from the handle's present state: the
      * fused launch into a scratch destination and the history update.  Neither the ring nor the handle's position or history changes. */
     int gsh_cond_time_push(gsh_cond_t* h, const void* device_block, uint64_t n_in, int reps, float* avg_ms);
+    /* ---- pulse blanking as a stage of the conditioner's push (Pulse_Blanking_Filter: pulse_blanking_filter.cc:73-125, an optional xlating
+     * filter with decimation 1 in front of pulse_blanking_cc; here behind whatever filter the conf names).  With y the filter-output stream of the
+     * chain above (the decoded samples themselves when n_taps = 0): y is tiled into segments of `length` samples from y[0] on; the energy and the
+     * decision of a segment are those of gsh_pb_process_device over the whole stream (pulse_blanking_cc.cc:63-95), the state lives in device
+     * memory and is carried from push to push; z[k] = (0, 0) where the segment of k was blanked, else y[k]; the resampler gathers from z with the
+     * same m(j).  Only whole segments are emitted and a trailing partial one waits for the next push (it is never flushed): after N inputs and
+     * M = ceil(N / D) filter outputs, M' = floor(M / length) * length are mitigated and the ring has every j with m(j) < M'.
+     * Invariant: the ring holds, bit for bit, what the loose chain gives with gsh_pb_process_device between the filter and the resampler, one call
+     * per stage over the concatenated input, and gsh_cond_blanking_state equals gsh_pb_get_state of that run.  One difference in timing, not in
+     * content: gsh_pb_process_device, like the block, leaves a segment that ends exactly on the last offered item for its next call; the
+     * conditioner emits it. */
+    typedef struct
+    {
+        float pfa;                /* in (0, 1) */
+        int32_t length;           /* 1..4096 samples per segment */
+        int32_t n_segments_est;   /* >= 0 */
+        int32_t n_segments_reset; /* >= 0 */
+    } gsh_cond_blanking;
+    struct gsh_cond_blanking_state /* a struct tag: the entry point that fills it has the same name */
+    {
+        float thres;                  /* gsh_pb_threshold */
+        float noise_power_estimation; /* as gsh_pb_get_state */
+        int32_t n_segments;
+        int32_t last_filtered;
+        uint64_t n_decided;           /* segments decided since the handle was created */
+        uint64_t n_blanked;           /* ... and those of them that were blanked */
+    };
+    /* Allowed until the handle's first push (GSH_ERR_STATE afterwards); GSH_ERR_INVALID with a message for values outside gsh_pb_create's ranges,
+     * before anything is allocated.  NULL turns the stage off again.  The push entry points, _position, _bind and _time_push keep their rules; a
+     * push that completes no segment returns *n_out = 0. */
+    int gsh_cond_set_blanking(gsh_cond_t* h, const gsh_cond_blanking* blanking);
+    /* gsh_cond_plan for a chain with the stage (NULL: without it) */
+    int gsh_cond_plan_blanked(const gsh_cond_conf* conf, const gsh_cond_blanking* blanking, uint64_t n_in_total, uint64_t* n_out_total);
+    /* waits for the handle's queued pushes, then reads the state.  GSH_ERR_STATE on a handle without the stage. */
+    int gsh_cond_blanking_state(gsh_cond_t* h, struct gsh_cond_blanking_state* state);
     /* ---- signal generator: synthetic GNSS scenarios made on the device (Signal_Generator: src/algorithms/signal_generator/adapters/
      * signal_generator.cc over gnuradio_blocks/signal_generator_c.h / .cc = sg.cc), into a caller's device buffer or straight into a ring.
      * Table-driven.  A generator holds n_sats <= GSH_GEN_MAX_SATS satellites; a satellite is two complex64 tables A and B of `period` samples
