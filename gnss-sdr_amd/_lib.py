@@ -209,6 +209,33 @@ class CondBlankingState(C.Structure):
     ]
 
 
+class CondNotch(C.Structure):
+    """gsh_cond_notch (24 bytes): the conditioner's notch stage."""
+    _fields_ = [
+        ("pfa", C.c_float),
+        ("p_c_factor", C.c_float),
+        ("length", C.c_int32),
+        ("n_segments_est", C.c_int32),
+        ("n_segments_reset", C.c_int32),
+        ("n_segments_coeff", C.c_int32),
+    ]
+
+
+class CondNotchState(C.Structure):
+    """struct gsh_cond_notch_state (48 bytes)."""
+    _fields_ = [
+        ("thres", C.c_float),
+        ("noise_pow_est", C.c_float),
+        ("n_segments", C.c_int32),
+        ("filter_state", C.c_int32),
+        ("n_segments_coeff", C.c_int32),
+        ("reserved", C.c_int32),
+        ("z0", C.c_float * 2),
+        ("n_decided", C.c_uint64),
+        ("n_filtered", C.c_uint64),
+    ]
+
+
 class AcqResult(C.Structure):
     """gsh_acq_result."""
     _fields_ = [
@@ -350,6 +377,9 @@ SYMBOLS = {
     "gsh_cond_set_blanking": (C.c_int, [_P, C.POINTER(CondBlanking)]),
     "gsh_cond_plan_blanked": (C.c_int, [C.POINTER(CondConf), C.POINTER(CondBlanking), C.c_uint64, C.POINTER(C.c_uint64)]),
     "gsh_cond_blanking_state": (C.c_int, [_P, C.POINTER(CondBlankingState)]),
+    "gsh_cond_set_notch": (C.c_int, [_P, C.POINTER(CondNotch)]),
+    "gsh_cond_plan_notched": (C.c_int, [C.POINTER(CondConf), C.POINTER(CondNotch), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gsh_cond_notch_state": (C.c_int, [_P, C.POINTER(CondNotchState)]),
     "gsh_gen_create": (C.c_int, [C.c_int, C.c_double, C.c_int32, C.POINTER(_P)]),
     "gsh_gen_destroy": (None, [_P]),
     "gsh_gen_set_satellite": (C.c_int, [_P, C.c_int32, _F, _F, C.c_uint32, C.c_uint32, _I8, C.c_int32, _I8, C.c_int32, C.c_double, C.c_double, C.c_double]),

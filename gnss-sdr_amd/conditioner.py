@@ -58,14 +58,34 @@ def _blanking(blanking):
     return _lib.CondBlanking(float(b["pfa"]), int(b["length"]), int(b["segments_est"]), int(b["segments_reset"]))
 
 
+# notch_filter.cc:41-51 / notch_filter_lite.cc:41-55; segments_coeff 0: Notch_Filter, >= 1: Notch_Filter_Lite with that n_segments_coeff
+NOTCH_DEFAULTS = dict(pfa=0.001, p_c_factor=0.9, length=32, segments_est=12500, segments_reset=5000000, segments_coeff=0)
+
+
+def _notch(notch):
+    """None or the property names of Notch_Filter / Notch_Filter_Lite (pfa, p_c_factor, length, segments_est, segments_reset; segments_coeff >= 1
+    for NotchLite; defaults of the reference) -> gsh_cond_notch"""
+    if notch is None:
+        return None
+    unknown = set(notch) - set(NOTCH_DEFAULTS)
+    if unknown:
+        raise ValueError(f"notch: unknown keys {sorted(unknown)} (known: {', '.join(NOTCH_DEFAULTS)})")
+    n = dict(NOTCH_DEFAULTS, **notch)
+    return _lib.CondNotch(float(n["pfa"]), float(n["p_c_factor"]), int(n["length"]), int(n["segments_est"]), int(n["segments_reset"]), int(n["segments_coeff"]))
+
+
 def outputs_after(n_in_total: int, input_kind="gr_complex", inverted_spectrum: bool = False, taps=None, decimation: int = 1, center_freq_hz: float = 0.0,
-                  sampling_freq_hz: float = 1.0, fs_in: float = 0.0, fs_out: float = 0.0, blanking=None) -> int:
-    """gsh_cond_plan / gsh_cond_plan_blanked: ring samples such a conditioner has produced once n_in_total input samples have arrived.  Host
-    arithmetic, no GPU."""
+                  sampling_freq_hz: float = 1.0, fs_in: float = 0.0, fs_out: float = 0.0, blanking=None, notch=None) -> int:
+    """gsh_cond_plan / gsh_cond_plan_blanked / gsh_cond_plan_notched: ring samples such a conditioner has produced once n_in_total input samples
+    have arrived.  Host arithmetic, no GPU."""
     c, _t = _conf(input_kind, inverted_spectrum, taps, decimation, center_freq_hz, sampling_freq_hz, fs_in, fs_out)
     out = C.c_uint64(0)
-    b = _blanking(blanking)
-    if b is None:
+    b, n = _blanking(blanking), _notch(notch)
+    if b is not None and n is not None:
+        raise ValueError("blanking and notch: one mitigation stage per conditioner")
+    if n is not None:
+        check(_lib.load().gsh_cond_plan_notched(C.byref(c), C.byref(n), int(n_in_total), C.byref(out)))
+    elif b is None:
         check(_lib.load().gsh_cond_plan(C.byref(c), int(n_in_total), C.byref(out)))
     else:
         check(_lib.load().gsh_cond_plan_blanked(C.byref(c), C.byref(b), int(n_in_total), C.byref(out)))
@@ -77,25 +97,31 @@ class SignalConditioner:
     need a filter) or a PackedFormat.  taps None or empty: no filter.  fs_in = fs_out = 0: no resampler (fs_in is the rate after the filter).
     blanking: None, or dict(pfa=0.04, length=32, segments_est=12500, segments_reset=5000000) (any subset): pulse blanking (Pulse_Blanking_Filter)
     between the filter and the resampler; whole segments of `length` filter outputs are emitted, a partial one waits for the next push.
+    notch: None, or dict(pfa=0.001, p_c_factor=0.9, length=32, segments_est=12500, segments_reset=5000000, segments_coeff=0) (any subset): the notch
+    filter (Notch_Filter; segments_coeff >= 1: Notch_Filter_Lite) in that place instead; output k is the mitigated filter output k + 1, whole
+    segments only.  One of blanking / notch per handle.
     Every push returns (first_out, n_out): the ring index of the block's first output and how many outputs it completed."""
 
     def __init__(self, ring: SampleStream | None = None, input_kind="gr_complex", inverted_spectrum: bool = False, taps=None, decimation: int = 1,
-                 center_freq_hz: float = 0.0, sampling_freq_hz: float = 1.0, fs_in: float = 0.0, fs_out: float = 0.0, device: int = 0, blanking=None):
+                 center_freq_hz: float = 0.0, sampling_freq_hz: float = 1.0, fs_in: float = 0.0, fs_out: float = 0.0, device: int = 0, blanking=None,
+                 notch=None):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.input_kind = input_kind
         c, _t = _conf(input_kind, inverted_spectrum, taps, decimation, center_freq_hz, sampling_freq_hz, fs_in, fs_out)
         self._np = None if c.input == INPUT_PACKED else _REAL_NP[c.item_type] if c.input == INPUT_REAL else _ITEM_NP[c.item_type]
         self._per_sample = 1 if c.input != INPUT_ITEMS or c.item_type == 0 else 2   # array elements per input sample
-        b = _blanking(blanking)
+        b, n = _blanking(blanking), _notch(notch)
         check(self._lib.gsh_cond_create(device, C.byref(c), C.byref(self._h)))
         self.ring = None
-        if b is not None:
-            try:
+        try:
+            if b is not None:
                 check(self._lib.gsh_cond_set_blanking(self._h, C.byref(b)))
-            except Exception:
-                self.close()
-                raise
+            if n is not None:
+                check(self._lib.gsh_cond_set_notch(self._h, C.byref(n)))   # (with blanking as well: GSH_ERR_STATE, one mitigation stage per handle)
+        except Exception:
+            self.close()
+            raise
         if ring is not None:
             self.bind(ring)
 
@@ -107,8 +133,8 @@ class SignalConditioner:
           InputFilter      Pass_Through | Fir_Filter | Freq_Xlating_Fir_Filter with input_item_type, decimation_factor, IF, sampling_frequency
                            (freq_xlating_fir_filter.cc:62-75) and `taps`: the caller's (firdes_low_pass, or a Remez design made on the host)
           Resampler        Pass_Through | Direct_Resampler with sample_freq_in, sample_freq_out (direct_resampler_conditioner.cc:36-43)
-        ValueError for an implementation this mapping does not cover: Notch_Filter, Notch_Filter_Lite stay loose calls (NotchFilter), and
-        Pulse_Blanking_Filter is mapped by properties_with_mitigation()."""
+        ValueError for an implementation this mapping does not cover: Pulse_Blanking_Filter is mapped by properties_with_mitigation(), Notch_Filter
+        and Notch_Filter_Lite by properties_with_notch()."""
         ada, fil, res = (dict(role.get(k, {})) for k in ("DataTypeAdapter", "InputFilter", "Resampler"))
         a_impl, f_impl, r_impl = (d.get("implementation", "Pass_Through") for d in (ada, fil, res))
         if a_impl not in ADAPTERS:
@@ -171,6 +197,57 @@ class SignalConditioner:
     @classmethod
     def from_properties_with_mitigation(cls, ring: SampleStream | None, role: dict, device: int = 0) -> "SignalConditioner":
         return cls(ring, device=device, **cls.properties_with_mitigation(role))
+
+    @staticmethod
+    def properties_with_notch(role: dict) -> dict:
+        """properties_with_mitigation() with InputFilter.implementation = Notch_Filter | Notch_Filter_Lite covered as well (notch_filter.cc:41-56,
+        notch_filter_lite.cc:41-61):
+          pfa, p_c_factor, length, segments_est, segments_reset   the `notch` keyword (defaults 0.001, 0.9, 32, 12500, 5000000)
+          coeff_rate, sampling_frequency                          Notch_Filter_Lite: n_segments_coeff = max(1, int((sampling_frequency / coeff_rate)
+                                                                  / length)) in float32; coeff_rate defaults to 0.1 sampling_frequency, that (the
+                                                                  reference reads SignalSource.sampling_frequency) to 4000000
+          item_type                                               gr_complex only
+        Neither adapter puts a filter in front of the block.  Every other implementation is delegated to properties_with_mitigation()."""
+        fil = dict(role.get("InputFilter", {}))
+        impl = fil.get("implementation", "Pass_Through")
+        if impl not in ("Notch_Filter", "Notch_Filter_Lite"):
+            return SignalConditioner.properties_with_mitigation(role)
+        if fil.get("item_type", "gr_complex") != "gr_complex":
+            raise ValueError(f"InputFilter.item_type {fil['item_type']!r}: {impl} takes gr_complex only")
+        kw = SignalConditioner.properties({k: v for k, v in role.items() if k != "InputFilter"})
+        if kw["input_kind"] not in ("gr_complex", "ibyte", "ishort"):
+            raise ValueError(f"{impl} takes gr_complex, the adapter yields {kw['input_kind']!r}")
+        notch = {k: type(d)(fil.get(k, d)) for k, d in NOTCH_DEFAULTS.items() if k != "segments_coeff"}
+        notch["segments_coeff"] = 0
+        if impl == "Notch_Filter_Lite":
+            f32 = np.float32
+            samp_freq = f32(fil.get("sampling_frequency", 4000000.0))
+            coeff_rate = f32(fil.get("coeff_rate", f32(samp_freq * f32(0.1))))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ratio = f32(f32(samp_freq / coeff_rate) / f32(notch["length"]))
+            if not np.isfinite(ratio):
+                raise ValueError(f"InputFilter.coeff_rate {float(coeff_rate)!r} and length {notch['length']!r} give no coefficient count")
+            notch["segments_coeff"] = max(1, int(ratio))
+        kw["notch"] = notch
+        return kw
+
+    @classmethod
+    def from_properties_with_notch(cls, ring: SampleStream | None, role: dict, device: int = 0) -> "SignalConditioner":
+        return cls(ring, device=device, **cls.properties_with_notch(role))
+
+    def set_notch(self, notch) -> None:
+        """gsh_cond_set_notch: before the first push only, and not while blanking is on; None turns the stage off"""
+        n = _notch(notch)
+        check(self._lib.gsh_cond_set_notch(self._h, C.byref(n) if n is not None else None))
+
+    def notch_state(self) -> dict:
+        """gsh_cond_notch_state (waits for the queued pushes): thres, noise_pow_est, n_segments, filter_state, n_segments_coeff, z0 (NotchLite's
+        coefficient; 0 for Notch) and the counters n_decided / n_filtered -- the duty cycle of the filter"""
+        s = _lib.CondNotchState()
+        check(self._lib.gsh_cond_notch_state(self._h, C.byref(s)))
+        return dict(thres=np.float32(s.thres), noise_pow_est=np.float32(s.noise_pow_est), n_segments=int(s.n_segments), filter_state=bool(s.filter_state),
+                    n_segments_coeff=int(s.n_segments_coeff), z0=np.complex64(complex(s.z0[0], s.z0[1])), n_decided=int(s.n_decided),
+                    n_filtered=int(s.n_filtered))
 
     def set_blanking(self, blanking) -> None:
         """gsh_cond_set_blanking: before the first push only; None turns the stage off"""

@@ -4,6 +4,7 @@
 #ifndef GSH_CONDITIONER_H
 #define GSH_CONDITIONER_H
 #include "gsh_internal.h"
+#include "notch_filter.h"
 #include "packed_unpack.h"
 
 namespace gsh
@@ -88,6 +89,54 @@ int cond_blank_launch_decide(const CondBlankArgs& b, hipStream_t st);
 // queue the gather: ring samples [a.out0, a.out0 + a.n_out) into a.out, each mask ? 0 : stage[m(j) - base] (a: q0, r0 planned; every m(j) within
 // the decided segments)
 int cond_blank_launch_gather(const CondArgs& a, const CondBlankArgs& b, hipStream_t st);
+
+// ---- the notch stage (cond_notch.hip): notch_cc / notch_lite_cc between the filter and the resampler.  Notch output w[k] is the mitigated filter
+// output y[k + 1] with y[k] in front of it; w is cut into segments of `length` from w[0] on and into chunks of NF_CHUNK from w[0] on.  A push forms
+// its new filter outputs behind the carried ones (y from the start of the open chunk on) in a stage buffer x, whose item 0 is filter output
+// `origin`: the first sample of the segment the open chunk starts in, so that index k - origin of x, mode and z0_seg addresses w[k] the way
+// sample_map (notch_filter.h) addresses a call's sample.  Then: energy and floor of the segments the push completes, their decision, the
+// composites of the chunks from the open one on, the carry chain, the replay that writes the push's new outputs, and the gather into the ring.
+struct CondNotchState          // device memory, carried from push to push
+{
+    NotchState s;              // (last_out and Notch's per-sample z0 are not kept: they depend on where a call ends)
+    unsigned long long n_decided, n_filtered;  // segments decided since the handle was created, and those of them that went through the recurrence
+    float2 carry;              // the recurrence's value in front of the open chunk: a chain of chunk composites, never a replayed output
+};
+struct CondNotchArgs
+{
+    float2* x;                 // filter outputs origin, origin + 1, ...; those below y0 are never formed nor read
+    float* energy;             // n_seg
+    float* floor_lin;          // n_seg
+    unsigned char* mode;       // per segment from seg_base on: the carried ones, then the n_seg new ones
+    float2* z0_seg;            // (NotchLite) likewise
+    float2* comp;              // per chunk from c0 on: (B, A) composites, then the carries
+    float2* w;                 // notch outputs W0 .. W1
+    const float2* y_in;        // carried filter outputs y0 .. y0 + n_y_in, modes and coefficients of segments seg_base .. S0
+    const unsigned char* mode_in;
+    const float2* z0_in;
+    float2* y_out;             // what the push leaves: filter outputs y1 .. y1 + n_y_out, modes and coefficients of segments seg_base1 .. S0 + n_seg
+    unsigned char* mode_out;
+    float2* z0_out;
+    const CondNotchState* state_in;
+    CondNotchState* state_out; // (gsh_cond_time_push: a copy)
+    unsigned long long origin, seg_base;  // origin = seg_base * length
+    unsigned long long y0, n_y_in;        // y0 = c0 * NF_CHUNK
+    unsigned long long y1, n_y_out, seg_base1;
+    unsigned long long S0, n_seg;         // first segment the push completes, and how many
+    unsigned long long W0, W1;            // = S0 * length, (S0 + n_seg) * length
+    unsigned long long c0, n_chunks;      // chunks c0 .. c0 + n_chunks cover [y0, W1); the first n_full of them are whole
+    unsigned long long n_full;
+    int length, n_segments_est, n_segments_reset, n_segments_coeff;
+    float thres, p_c_factor;
+};
+// queue the copy of the carried filter outputs, modes and coefficients into x, mode, z0_seg (before the push's filter outputs are formed behind them)
+int cond_notch_launch_load(const CondNotchArgs& n, hipStream_t st);
+// queue segment kernel, decision, compose, carry and replay of n.n_seg > 0 segments
+int cond_notch_launch_filter(const CondNotchArgs& n, hipStream_t st);
+// queue the copy of what the next push needs into y_out, mode_out, z0_out
+int cond_notch_launch_save(const CondNotchArgs& n, hipStream_t st);
+// queue the gather: ring samples [a.out0, a.out0 + a.n_out) into a.out, each w[m(j) - W0] (a: q0, r0 planned; every m(j) within [W0, W1))
+int cond_notch_launch_gather(const CondArgs& a, const CondNotchArgs& n, hipStream_t st);
 
 // q0, r0 of a launch whose first output is a.out0 (a.step, a.rs_mode set)
 void cond_plan_resampler(CondArgs* a);

@@ -15,11 +15,18 @@
 // of M above.  A push forms every new filter output behind the carry of the open segment (at most L - 1 outputs, kept in device memory,
 // double-buffered and ordered by the same event as the history) in the handle's stage buffer, decides the segments these complete on the device, and
 // gathers mask ? 0 : stage[m(j) - base] into the ring; the state never comes back to the host.
+//
+// With the notch stage (gsh_cond_set_notch; kernels in cond_notch.hip) the resampler sees W' = floor((M - 1) / L) L notch outputs in place of M: output
+// k is the mitigated filter output k + 1, and a segment is decided once its last sample is there.  The recurrence is chained over chunks of NF_CHUNK
+// outputs counted from output 0, so a push keeps, in device memory and double-buffered like the history, the filter outputs from the start of the
+// open chunk on, the modes (NotchLite: and coefficients) of the decided segments that overlap it, and in the state the carry in front of it; it
+// forms the chunk again from its start and writes the outputs that are new.
 #include "conditioner.h"
 #include "pulse_blanking.h"
 #include "resample_index.h"
 #include "sample_convert.h"
 #include "sample_stream.h"
+#include <cmath>
 #include <new>
 
 namespace
@@ -106,11 +113,12 @@ unsigned long long filter_outputs_after(const CondPlan& p, unsigned long long n_
 }
 
 // ring samples produced once n_in input samples have arrived (see the head of the file); length > 0: with the blanking stage, which hands the
-// resampler whole segments only
-unsigned long long outputs_after(const CondPlan& p, unsigned long long n_in, int length = 0)
+// resampler whole segments only; notch_length > 0: with the notch stage, whose segments need one more filter output
+unsigned long long outputs_after(const CondPlan& p, unsigned long long n_in, int length = 0, int notch_length = 0)
 {
     unsigned long long M = filter_outputs_after(p, n_in);
     if (length > 0) M -= M % static_cast<unsigned long long>(length);
+    if (notch_length > 0) M = M == 0 ? 0 : (M - 1) - (M - 1) % static_cast<unsigned long long>(notch_length);
     if (M == 0 || p.rs_mode == gsh::COND_RS_NONE) return M;
     if (p.rs_mode == gsh::COND_RS_DECIMATE) return static_cast<unsigned long long>((static_cast<unsigned __int128>(M - 1) * p.step) >> 32) + 1;
     return static_cast<unsigned long long>(((static_cast<unsigned __int128>(M) << 32) + p.step - 1) / p.step) - 1;
@@ -131,6 +139,29 @@ struct BlankFrame
     unsigned long long M0, base, c0;  // filter outputs before the push, the mitigated ones of them, the carry M0 - base
     unsigned long long n_new;         // filter outputs the push completes
     unsigned long long n_seg, c1;     // segments it completes, and the carry it leaves
+};
+
+// gsh_notch_create's ranges
+int check_notch(const gsh_cond_notch* n)
+{
+    GSH_REQUIRE(n->pfa > 0.0f && n->pfa < 1.0f, "pfa %g outside (0, 1)", static_cast<double>(n->pfa));
+    GSH_REQUIRE(n->length >= 2 && n->length <= 1024, "length %d outside 2..1024", n->length);
+    GSH_REQUIRE(n->n_segments_est >= 0 && n->n_segments_reset >= 0 && n->n_segments_coeff >= 0, "negative segment count");
+    GSH_REQUIRE(std::isfinite(n->p_c_factor), "p_c_factor is not finite");
+    return GSH_OK;
+}
+
+constexpr unsigned long long NOTCH_CARRY_MODES = 66;  // decided segments that overlap the open chunk: fewer than NF_CHUNK / length + 1
+
+// what a push of n_in samples does to the notch stage (the names of CondNotchArgs, conditioner.h)
+struct NotchFrame
+{
+    unsigned long long M0, n_new;         // filter outputs before the push, and those it completes
+    unsigned long long S0, n_seg;         // segments decided before the push, and those it decides
+    unsigned long long W0, W1;            // notch outputs before and after
+    unsigned long long c0, y0, seg_base, origin, n_y_in;
+    unsigned long long y1, seg_base1, n_y_out;
+    unsigned long long n_chunks, n_full;
 };
 }  // namespace
 
@@ -169,6 +200,25 @@ struct gsh_cond
     size_t energy_cap{0};
     void* d_mask{nullptr};
     size_t mask_cap{0};
+    // the notch stage (gsh_cond_set_notch); it shares stage_tile / stage_span, d_y and d_energy with the blanking stage: a handle has one of the two
+    bool notch_on{false};
+    gsh_cond_notch notch{};
+    float notch_thres{0.0f};
+    gsh::CondNotchState* d_nstate{nullptr};   // [0] the state, [1] the copy gsh_cond_time_push writes
+    float2* d_ycarry[2]{nullptr, nullptr};    // filter outputs from the start of the open chunk on; these three double-buffered like the history
+    unsigned char* d_mcarry[2]{nullptr, nullptr};  // modes of the decided segments that overlap the open chunk
+    float2* d_zcarry[2]{nullptr, nullptr};    // (NotchLite) their coefficients
+    int notch_cur{0};
+    void* d_floor{nullptr};
+    size_t floor_cap{0};
+    void* d_mode{nullptr};
+    size_t mode_cap{0};
+    void* d_z0{nullptr};
+    size_t z0_cap{0};
+    void* d_comp{nullptr};
+    size_t comp_cap{0};
+    void* d_w{nullptr};                       // the notch outputs a push adds
+    size_t w_cap{0};
 };
 
 namespace
@@ -181,6 +231,23 @@ int block_bytes(const gsh_cond* h, unsigned long long n_in, unsigned long long* 
     return GSH_OK;
 }
 
+// ring samples the handle's chain, with its stage, has produced once n_in_total input samples have arrived
+unsigned long long outputs_total(const gsh_cond* h, unsigned long long n_in_total)
+{
+    return outputs_after(h->plan, n_in_total, h->blank_on ? h->blank.length : 0, h->notch_on ? h->notch.length : 0);
+}
+
+// a stage's buffer of filter outputs is indexed with 32 bits
+int check_stage_span(const gsh_cond* h, unsigned long long n_in)
+{
+    if (h->blank_on)
+        GSH_REQUIRE(filter_outputs_after(h->plan, n_in) + static_cast<unsigned long long>(h->blank.length) < (1ull << 32), "more than 2^32 filter outputs in one push");
+    if (h->notch_on)
+        GSH_REQUIRE(filter_outputs_after(h->plan, n_in) + 2ull * static_cast<unsigned long long>(h->notch.length) + gsh::NF_CHUNK < (1ull << 32),
+            "more than 2^32 filter outputs in one push");
+    return GSH_OK;
+}
+
 // the arguments of a push, all or nothing: *count = ring samples it completes
 int check_push(const gsh_cond* h, const void* items, unsigned long long n_in, unsigned long long* bytes, unsigned long long* count)
 {
@@ -189,9 +256,9 @@ int check_push(const gsh_cond* h, const void* items, unsigned long long n_in, un
     GSH_REQUIRE(h->ring != nullptr, "no ring bound (gsh_cond_bind)");
     int rc = block_bytes(h, n_in, bytes);
     if (rc != GSH_OK) return rc;
-    *count = outputs_after(h->plan, h->n_in_total + n_in, h->blank_on ? h->blank.length : 0) - h->n_out_total;
-    if (h->blank_on)
-        GSH_REQUIRE(filter_outputs_after(h->plan, n_in) + static_cast<unsigned long long>(h->blank.length) < (1ull << 32), "more than 2^32 filter outputs in one push");
+    *count = outputs_total(h, h->n_in_total + n_in) - h->n_out_total;
+    rc = check_stage_span(h, n_in);
+    if (rc != GSH_OK) return rc;
     gsh_stream* ring = h->ring;
     rc = gsh::stream_multi_check_rings(&ring, 1, *count);
     if (rc != GSH_OK) return rc;
@@ -327,12 +394,137 @@ int write_segment_blanked(void* ctx, unsigned long long first, unsigned long lon
     return gsh::cond_blank_launch_gather(a, c->b, st);
 }
 
+NotchFrame notch_frame(const gsh_cond* h, unsigned long long n_in)
+{
+    const unsigned long long L = static_cast<unsigned long long>(h->notch.length), C = gsh::NF_CHUNK;
+    NotchFrame f;
+    f.M0 = filter_outputs_after(h->plan, h->n_in_total);
+    const unsigned long long M1 = filter_outputs_after(h->plan, h->n_in_total + n_in);
+    f.n_new = M1 - f.M0;
+    f.S0 = f.M0 == 0 ? 0 : (f.M0 - 1) / L;
+    const unsigned long long S1 = M1 == 0 ? 0 : (M1 - 1) / L;
+    f.n_seg = S1 - f.S0;
+    f.W0 = f.S0 * L;
+    f.W1 = S1 * L;
+    f.c0 = f.W0 / C;
+    f.y0 = f.c0 * C;
+    f.seg_base = f.y0 / L;
+    f.origin = f.seg_base * L;
+    f.n_y_in = f.M0 - f.y0;          // (M0 > W0 >= y0 once there is a filter output; 0 - 0 before)
+    const unsigned long long c1 = f.W1 / C;
+    f.y1 = c1 * C;
+    f.seg_base1 = f.y1 / L;
+    f.n_y_out = M1 - f.y1;           // at most NF_CHUNK - 1 + length: M1 <= W1 + length, W1 - y1 < NF_CHUNK
+    f.n_full = c1 - f.c0;
+    f.n_chunks = (f.W1 + C - 1) / C - f.c0;
+    return f;
+}
+
+// the handle's buffers for a frame, before anything is queued
+int notch_reserve(gsh_cond* h, const NotchFrame& f)
+{
+    const unsigned long long n_modes = f.S0 - f.seg_base + f.n_seg;
+    int rc = grow(&h->d_y, &h->y_cap, sizeof(float2) * (f.y0 - f.origin + f.n_y_in + f.n_new));
+    if (rc == GSH_OK) rc = grow(&h->d_energy, &h->energy_cap, sizeof(float) * f.n_seg);
+    if (rc == GSH_OK) rc = grow(&h->d_floor, &h->floor_cap, sizeof(float) * f.n_seg);
+    if (rc == GSH_OK) rc = grow(&h->d_mode, &h->mode_cap, n_modes);
+    if (rc == GSH_OK) rc = grow(&h->d_z0, &h->z0_cap, sizeof(float2) * n_modes);
+    if (rc == GSH_OK) rc = grow(&h->d_comp, &h->comp_cap, sizeof(float2) * 2 * f.n_chunks);
+    if (rc == GSH_OK) rc = grow(&h->d_w, &h->w_cap, sizeof(float2) * (f.W1 - f.W0));
+    return rc;
+}
+
+// queue the carried filter outputs, the push's filter outputs behind them, the stage's launches over the segments they complete, and what the push
+// leaves for the next one in the other halves; *n = what the gather needs
+int notch_stage(const gsh_cond* h, const CondArgs& block, const NotchFrame& f, gsh::CondNotchState* state_out, hipStream_t st, gsh::CondNotchArgs* n)
+{
+    const int in = h->notch_cur, out = h->notch_cur ^ 1;
+    n->x = static_cast<float2*>(h->d_y);
+    n->energy = static_cast<float*>(h->d_energy);
+    n->floor_lin = static_cast<float*>(h->d_floor);
+    n->mode = static_cast<unsigned char*>(h->d_mode);
+    n->z0_seg = static_cast<float2*>(h->d_z0);
+    n->comp = static_cast<float2*>(h->d_comp);
+    n->w = static_cast<float2*>(h->d_w);
+    n->y_in = h->d_ycarry[in];
+    n->mode_in = h->d_mcarry[in];
+    n->z0_in = h->d_zcarry[in];
+    n->y_out = h->d_ycarry[out];
+    n->mode_out = h->d_mcarry[out];
+    n->z0_out = h->d_zcarry[out];
+    n->state_in = h->d_nstate;
+    n->state_out = state_out;
+    n->origin = f.origin;
+    n->seg_base = f.seg_base;
+    n->y0 = f.y0;
+    n->n_y_in = f.n_y_in;
+    n->y1 = f.y1;
+    n->n_y_out = f.n_y_out;
+    n->seg_base1 = f.seg_base1;
+    n->S0 = f.S0;
+    n->n_seg = f.n_seg;
+    n->W0 = f.W0;
+    n->W1 = f.W1;
+    n->c0 = f.c0;
+    n->n_chunks = f.n_chunks;
+    n->n_full = f.n_full;
+    n->length = h->notch.length;
+    n->n_segments_est = h->notch.n_segments_est;
+    n->n_segments_reset = h->notch.n_segments_reset;
+    n->n_segments_coeff = h->notch.n_segments_coeff;
+    n->thres = h->notch_thres;
+    n->p_c_factor = h->notch.p_c_factor;
+    int rc = gsh::cond_notch_launch_load(*n, st);
+    if (rc != GSH_OK) return rc;
+    if (f.n_new > 0)
+        {
+            CondArgs a = block;  // every filter output: the chain's launch without its resampler
+            a.rs_mode = gsh::COND_RS_NONE;
+            a.step = 0u;
+            a.q0 = a.r0 = 0;
+            a.tile = h->stage_tile;
+            a.max_span = h->stage_span;
+            a.out = n->x + (f.M0 - f.origin);
+            a.out0 = f.M0;
+            a.n_out = f.n_new;
+            rc = gsh::cond_launch(a, st);
+            if (rc != GSH_OK) return rc;
+        }
+    if (f.n_seg > 0)
+        {
+            rc = gsh::cond_notch_launch_filter(*n, st);
+            if (rc != GSH_OK) return rc;
+        }
+    return gsh::cond_notch_launch_save(*n, st);
+}
+
+struct NotchSegmentCtx
+{
+    CondArgs a;
+    unsigned long long out0;
+    gsh::CondNotchArgs n;
+};
+
+// MultiSegmentWriter of a push with the notch stage
+int write_segment_notched(void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t st)
+{
+    const NotchSegmentCtx* c = static_cast<const NotchSegmentCtx*>(ctx);
+    CondArgs a = c->a;
+    a.out = dst[0];
+    a.out0 = c->out0 + first;
+    a.n_out = len;
+    gsh::cond_plan_resampler(&a);
+    return gsh::cond_notch_launch_gather(a, c->n, st);
+}
+
 int push_block_blanked(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st);
+int push_block_notched(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st);
 
 // queue the device work of a checked push on st and advance the handle
 int push_block(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st)
 {
     if (h->blank_on) return push_block_blanked(h, d_block, n_in, count, st);
+    if (h->notch_on) return push_block_notched(h, d_block, n_in, count, st);
     if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
     SegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total};
     if (count > 0)
@@ -387,6 +579,37 @@ int push_block_blanked(gsh_cond* h, const void* d_block, unsigned long long n_in
     return GSH_OK;
 }
 
+int push_block_notched(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st)
+{
+    const NotchFrame f = notch_frame(h, n_in);
+    int rc = notch_reserve(h, f);
+    if (rc != GSH_OK) return rc;
+    if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
+    NotchSegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total, {}};
+    rc = notch_stage(h, ctx.a, f, h->d_nstate, st, &ctx.n);
+    if (rc != GSH_OK) return rc;
+    if (count > 0)
+        {
+            rc = gsh::stream_write_device_multi(&h->ring, 1, count, st, write_segment_notched, &ctx);
+            if (rc != GSH_OK) return rc;
+        }
+    if (n_in > 0)
+        {
+            if (h->plan.n_taps > 1)
+                {
+                    rc = gsh::cond_launch_history(ctx.a, st);
+                    if (rc != GSH_OK) return rc;
+                    h->cur ^= 1;
+                }
+            GSH_HIP(hipEventRecord(h->hist_ev, st));
+            h->hist_recorded = true;
+        }
+    h->notch_cur ^= 1;  // (the save wrote the other halves, an unchanged carry included)
+    h->n_in_total += n_in;
+    h->n_out_total += count;
+    return GSH_OK;
+}
+
 void report(const gsh_cond* h, unsigned long long count, uint64_t* first_out, uint64_t* n_out)
 {
     if (first_out) *first_out = h->ring_base + h->n_out_total;
@@ -431,6 +654,7 @@ extern "C"
             }
         int rc = check_blanking(blanking);
         if (rc != GSH_OK) return rc;
+        if (h->notch_on) return set_error(GSH_ERR_STATE, "the conditioner has a notch stage: one mitigation stage per handle (gsh_cond_set_notch(h, NULL) turns it off)");
         GSH_HIP(hipSetDevice(h->device));
         h->blank_on = false;
         if (h->d_bstate == nullptr) GSH_HIP(hipMalloc(&h->d_bstate, 2 * sizeof(gsh::CondBlankState)));
@@ -465,6 +689,81 @@ extern "C"
         state->last_filtered = s.last_filtered;
         state->n_decided = s.n_decided;
         state->n_blanked = s.n_blanked;
+        return GSH_OK;
+    }
+
+    int gsh_cond_plan_notched(const gsh_cond_conf* conf, const gsh_cond_notch* notch, uint64_t n_in_total, uint64_t* n_out_total)
+    {
+        if (notch == nullptr) return gsh_cond_plan(conf, n_in_total, n_out_total);
+        GSH_REQUIRE(n_out_total != nullptr, "null n_out_total");
+        *n_out_total = 0;
+        CondPlan p;
+        int rc = reduce_conf(conf, &p);
+        if (rc == GSH_OK) rc = check_notch(notch);
+        if (rc != GSH_OK) return rc;
+        *n_out_total = outputs_after(p, n_in_total, 0, notch->length);
+        return GSH_OK;
+    }
+
+    int gsh_cond_set_notch(gsh_cond_t* h, const gsh_cond_notch* notch)
+    {
+        GSH_REQUIRE(h != nullptr, "null conditioner");
+        if (h->n_in_total != 0 || h->hist_recorded) return set_error(GSH_ERR_STATE, "the notch stage is set before the handle's first push (%llu samples taken)", h->n_in_total);
+        if (notch == nullptr)
+            {
+                h->notch_on = false;
+                return GSH_OK;
+            }
+        int rc = check_notch(notch);
+        if (rc != GSH_OK) return rc;
+        if (h->blank_on) return set_error(GSH_ERR_STATE, "the conditioner has a blanking stage: one mitigation stage per handle (gsh_cond_set_blanking(h, NULL) turns it off)");
+        GSH_HIP(hipSetDevice(h->device));
+        h->notch_on = false;
+        if (h->d_nstate == nullptr) GSH_HIP(hipMalloc(&h->d_nstate, 2 * sizeof(gsh::CondNotchState)));
+        GSH_HIP(hipMemset(h->d_nstate, 0, 2 * sizeof(gsh::CondNotchState)));  // notch_cc.cc:41-51; the recurrence starts from 0
+        if (h->d_ycarry[0]) GSH_HIP(hipFree(h->d_ycarry[0]));
+        h->d_ycarry[0] = h->d_ycarry[1] = nullptr;
+        const size_t n_y = static_cast<size_t>(gsh::NF_CHUNK) + static_cast<size_t>(notch->length) + 1;  // NotchFrame::n_y_out at most
+        GSH_HIP(hipMalloc(&h->d_ycarry[0], sizeof(float2) * 2 * n_y));
+        h->d_ycarry[1] = h->d_ycarry[0] + n_y;
+        if (h->d_zcarry[0] == nullptr)
+            {
+                GSH_HIP(hipMalloc(&h->d_zcarry[0], (sizeof(float2) + 1) * 2 * NOTCH_CARRY_MODES));
+                h->d_zcarry[1] = h->d_zcarry[0] + NOTCH_CARRY_MODES;
+                h->d_mcarry[0] = reinterpret_cast<unsigned char*>(h->d_zcarry[1] + NOTCH_CARRY_MODES);
+                h->d_mcarry[1] = h->d_mcarry[0] + NOTCH_CARRY_MODES;
+            }
+        h->notch_cur = 0;
+        CondArgs a = h->base;
+        a.rs_mode = gsh::COND_RS_NONE;
+        gsh::cond_tile(&a);
+        h->stage_tile = a.tile;
+        h->stage_span = a.max_span;
+        h->notch = *notch;
+        h->notch_thres = gsh::nf_threshold(notch->pfa, notch->length);
+        h->notch_on = true;
+        return GSH_OK;
+    }
+
+    int gsh_cond_notch_state(gsh_cond_t* h, struct gsh_cond_notch_state* state)
+    {
+        GSH_REQUIRE(h != nullptr && state != nullptr, "null argument");
+        if (!h->notch_on) return set_error(GSH_ERR_STATE, "the conditioner has no notch stage (gsh_cond_set_notch)");
+        GSH_HIP(hipSetDevice(h->device));
+        if (h->hist_recorded) GSH_HIP(hipEventSynchronize(h->hist_ev));
+        gsh::CondNotchState s{};
+        GSH_HIP(hipMemcpy(&s, h->d_nstate, sizeof(s), hipMemcpyDeviceToHost));
+        const bool lite = h->notch.n_segments_coeff > 0;
+        state->thres = h->notch_thres;
+        state->noise_pow_est = s.s.noise_pow_est;
+        state->n_segments = s.s.n_segments;
+        state->filter_state = s.s.filter_state;
+        state->n_segments_coeff = s.s.n_segments_coeff;
+        state->reserved = 0;
+        state->z0[0] = lite ? s.s.z0.x : 0.0f;
+        state->z0[1] = lite ? s.s.z0.y : 0.0f;
+        state->n_decided = s.n_decided;
+        state->n_filtered = s.n_filtered;
         return GSH_OK;
     }
 
@@ -529,6 +828,11 @@ extern "C"
         if (h->d_y) (void)hipFree(h->d_y);
         if (h->d_energy) (void)hipFree(h->d_energy);
         if (h->d_mask) (void)hipFree(h->d_mask);
+        if (h->d_nstate) (void)hipFree(h->d_nstate);
+        if (h->d_ycarry[0]) (void)hipFree(h->d_ycarry[0]);
+        if (h->d_zcarry[0]) (void)hipFree(h->d_zcarry[0]);  // (the carried modes lie behind the coefficients)
+        for (void* q : {h->d_floor, h->d_mode, h->d_z0, h->d_comp, h->d_w})
+            if (q) (void)hipFree(q);
         for (int i = 0; i < COND_NSTAGE; i++)
             {
                 if (h->d_stage[i]) (void)hipFree(h->d_stage[i]);
@@ -628,17 +932,25 @@ extern "C"
         unsigned long long bytes = 0;
         int rc = block_bytes(h, n_in, &bytes);
         if (rc != GSH_OK) return rc;
-        const unsigned long long count = outputs_after(h->plan, h->n_in_total + n_in, h->blank_on ? h->blank.length : 0) - h->n_out_total;
+        const unsigned long long count = outputs_total(h, h->n_in_total + n_in) - h->n_out_total;
         GSH_REQUIRE(count >= 1 && count < (1ull << 32), "a block of %llu samples completes %llu outputs: nothing to time", static_cast<unsigned long long>(n_in), count);
+        rc = check_stage_span(h, n_in);
+        if (rc != GSH_OK) return rc;
         GSH_HIP(hipSetDevice(h->device));
         // the launches of a push, into a scratch destination instead of the ring; the history update lands in the half no push has flipped to (with
-        // the blanking stage: so does the carry, and the decision writes the copy of the state)
+        // the blanking or the notch stage: so does what the stage carries, and the decision writes the copy of the state)
         BlankFrame f{};
+        NotchFrame nf{};
         if (h->blank_on)
             {
-                GSH_REQUIRE(filter_outputs_after(h->plan, n_in) + static_cast<unsigned long long>(h->blank.length) < (1ull << 32), "more than 2^32 filter outputs in one push");
                 f = blank_frame(h, n_in);
                 rc = blank_reserve(h, f);
+                if (rc != GSH_OK) return rc;
+            }
+        if (h->notch_on)
+            {
+                nf = notch_frame(h, n_in);
+                rc = notch_reserve(h, nf);
                 if (rc != GSH_OK) return rc;
             }
         float2* d_out = nullptr;
@@ -658,6 +970,12 @@ extern "C"
                     gsh::CondBlankArgs b{};
                     r = blank_stage(h, a, f, h->d_bstate + 1, st, &b);
                     if (r == GSH_OK) r = gsh::cond_blank_launch_gather(a, b, st);
+                }
+            else if (h->notch_on)
+                {
+                    gsh::CondNotchArgs n{};
+                    r = notch_stage(h, a, nf, h->d_nstate + 1, st, &n);
+                    if (r == GSH_OK) r = gsh::cond_notch_launch_gather(a, n, st);
                 }
             else
                 r = gsh::cond_launch(a, st);

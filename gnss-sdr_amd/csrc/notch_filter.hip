@@ -17,7 +17,9 @@
 //   notch_apply_kernel     output is the first carry), each thread replays its chunk from its carry and writes the outputs.
 // Floating-point parity with the sequential reference: the per-sample expression is formed in the reference's order; chaining chunk composites
 // re-associates the recurrence (differences ~1e-7 relative, amplified by 1 / (1 - p)).
+// The per-segment and per-sample arithmetic is notch_filter.h, shared with the conditioner's notch stage (cond_notch.hip).
 #include "gsh_internal.h"
+#include "notch_filter.h"
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -39,15 +41,7 @@ struct gsh_notch
     size_t seg_capacity{0};
     float2* d_comp{nullptr};          // per chunk: (B, A) composites, then carries
     size_t chunk_capacity{0};
-    struct State
-    {
-        float noise_pow_est;
-        int n_segments;
-        int filter_state;
-        int n_segments_coeff;
-        float2 last_out;
-        float2 z0;
-    };
+    using State = gsh::NotchState;
     State* d_state{nullptr};
     State h_state{};  // shadow of the state after the last call (decides whether a call can reach an estimating segment)
 };
@@ -56,104 +50,14 @@ namespace gsh
 {
 namespace
 {
-constexpr int NF_THREADS = 256;
-constexpr int NF_CHUNK = 128;  // samples one thread chains sequentially
-
-__device__ __forceinline__ float2 cmul_ref(float2 a, float2 b)  // std::complex<float> product, one rounding per operation
-{
-    return make_float2(__fsub_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fadd_rn(__fmul_rn(a.x, b.y), __fmul_rn(a.y, b.x)));
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y)); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y)); }
-
-// z0 = exp(j atan2(Im c, Re c)), c = cur conj(prev)   (notch.cc:95-99; volk_32fc_x2_multiply_conjugate_32fc, volk_32fc_s32f_atan2_32f, std::exp)
-__device__ __forceinline__ float2 phase_step(float2 cur, float2 prev)
-{
-    const float cr = __fadd_rn(__fmul_rn(cur.x, prev.x), __fmul_rn(cur.y, prev.y));
-    const float ci = __fsub_rn(__fmul_rn(cur.y, prev.x), __fmul_rn(cur.x, prev.y));
-    const float ang = atan2f(ci, cr);
-    float s, c;
-    sincosf(ang, &s, &c);
-    return make_float2(c, s);
-}
-__device__ __forceinline__ float angle_step(float2 cur, float2 prev)
-{
-    const float cr = __fadd_rn(__fmul_rn(cur.x, prev.x), __fmul_rn(cur.y, prev.y));
-    const float ci = __fsub_rn(__fmul_rn(cur.y, prev.x), __fmul_rn(cur.x, prev.y));
-    return atan2f(ci, cr);
-}
-
 // x points at item 0 (the sample in front of the first one processed); segment s covers items 1 + s L .. s L + L
 __global__ __launch_bounds__(NF_THREADS) void notch_segment_kernel(const float2* __restrict__ x, int length, unsigned long long n_seg, float* __restrict__ energy,
     float* __restrict__ floor_lin, int with_floor, int seg_per_wg)
 {
     extern __shared__ float lds[];
-    float2* tw = reinterpret_cast<float2*>(lds);                        // length twiddles
-    float2* xs = tw + length;                                           // seg_per_wg * length samples
-    float* db = reinterpret_cast<float*>(xs + static_cast<size_t>(seg_per_wg) * length);  // seg_per_wg * length dB values
     const unsigned long long seg0 = static_cast<unsigned long long>(blockIdx.x) * seg_per_wg;
     const int segs = static_cast<int>(min(static_cast<unsigned long long>(seg_per_wg), n_seg - seg0));
-    const int count = segs * length;
-    const float2* __restrict__ cur = x + 1 + seg0 * length;
-    for (int i = threadIdx.x; i < count; i += NF_THREADS) xs[i] = cur[i];
-    if (with_floor)
-        for (int i = threadIdx.x; i < length; i += NF_THREADS)
-            {
-                float s, c;
-                sincospif(2.0f * static_cast<float>(i) / static_cast<float>(length), &s, &c);
-                tw[i] = make_float2(c, -s);
-            }
-    __syncthreads();
-    // energy: real part of volk_32fc_x2_conjugate_dot_prod_32fc(in, in) (notch.cc:87-88), float terms, double sum
-    for (int s = threadIdx.x; s < segs; s += NF_THREADS)
-        {
-            double e = 0.0;
-            for (int k = 0; k < length; k++)
-                {
-                    const float2 v = xs[s * length + (k + s) % length];
-                    e += static_cast<double>(__fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y)));
-                }
-            energy[seg0 + s] = static_cast<float>(e);
-        }
-    if (!with_floor) return;
-    // spectrum: bin k of segment s (notch.cc:77-79); 10 log10 through a base-2 logarithm like the VOLK kernel
-    for (int i = threadIdx.x; i < count; i += NF_THREADS)
-        {
-            const int s = i / length, k = i - s * length;
-            double ar = 0.0, ai = 0.0;
-            int m = 0;
-            for (int n = 0; n < length; n++)
-                {
-                    const float2 v = xs[s * length + n], w = tw[m];
-                    ar += static_cast<double>(v.x) * w.x - static_cast<double>(v.y) * w.y;
-                    ai += static_cast<double>(v.x) * w.y + static_cast<double>(v.y) * w.x;
-                    m += k;
-                    if (m >= length) m -= length;
-                }
-            const float re = static_cast<float>(ar), im = static_cast<float>(ai);
-            const float p = __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im));
-            db[i] = p > 0.0f ? __fmul_rn(3.01029995663981209120f, log2f(p)) : __fmul_rn(3.01029995663981209120f, -127.0f);
-        }
-    __syncthreads();
-    // volk_32f_s32f_calc_spectral_noise_floor_32f(&sig2dB, power_spect, 15.0, length) and notch.cc:82, sequential float sums as the kernel forms them
-    for (int s = threadIdx.x; s < segs; s += NF_THREADS)
-        {
-            const float* d = db + s * length;
-            float sum = 0.0f;
-            for (int k = 0; k < length; k++) sum = __fadd_rn(sum, d[k]);
-            const float mean_amp = __fadd_rn(__fdiv_rn(sum, static_cast<float>(length)), 15.0f);
-            sum = 0.0f;
-            int kept = length;
-            for (int k = 0; k < length; k++)
-                {
-                    if (d[k] <= mean_amp)
-                        sum = __fadd_rn(sum, d[k]);
-                    else
-                        kept--;
-                }
-            const float sig2db = kept == 0 ? mean_amp : __fdiv_rn(sum, static_cast<float>(kept));
-            floor_lin[seg0 + s] = __fdiv_rn(powf(10.0f, __fdiv_rn(sig2db, 10.0f)), static_cast<float>(2 * length));
-        }
+    nf_segment_workgroup(lds, x, length, seg0, segs, energy, floor_lin, with_floor, seg_per_wg, 0);
 }
 
 // notch.cc:72-118 / lite.cc:81-136, one segment after the other
@@ -163,78 +67,12 @@ __global__ void notch_decide_kernel(const float2* __restrict__ x, const float* _
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     gsh_notch::State s = *st;
-    const bool lite = n_segments_coeff_reset > 0;
-    for (unsigned long long i = 0; i < n_seg; i++)
+    if (!nf_decide_segments(x, energy, floor_lin, have_floor, n_seg, length, mode, z0_seg, s, n_segments_est, n_segments_reset, n_segments_coeff_reset, thres, nullptr))
         {
-            unsigned char m;
-            if ((s.n_segments < n_segments_est) && (s.filter_state == 0))
-                {
-                    if (!have_floor)
-                        {
-                            *need_floor = 1;  // the host sized this call without the floor values: it repeats the call with them (nothing was written yet)
-                            return;
-                        }
-                    s.noise_pow_est = __fdiv_rn(__fadd_rn(__fmul_rn(static_cast<float>(s.n_segments), s.noise_pow_est), floor_lin[i]), static_cast<float>(s.n_segments + 1));
-                    m = 0;
-                }
-            else
-                {
-                    if (__fdiv_rn(energy[i], s.noise_pow_est) > thres)
-                        {
-                            m = 1;
-                            if (s.filter_state == 0)
-                                {
-                                    s.filter_state = 1;
-                                    m |= 0x80;  // last_out_ = 0
-                                    s.n_segments_coeff = 0;
-                                }
-                            if (lite)
-                                {
-                                    if (s.n_segments_coeff == 0)
-                                        {
-                                            const float2* cur = x + 1 + i * length;
-                                            const float a1 = angle_step(cur[1], cur[0]);
-                                            const float a2 = angle_step(cur[length - 1], cur[length - 2]);
-                                            const float ang = __fdiv_rn(__fadd_rn(a1, a2), 2.0f);
-                                            float sn, cs;
-                                            sincosf(ang, &sn, &cs);
-                                            s.z0 = make_float2(cs, sn);
-                                        }
-                                    z0_seg[i] = s.z0;
-                                    s.n_segments_coeff = (s.n_segments_coeff + 1) % n_segments_coeff_reset;
-                                }
-                        }
-                    else
-                        {
-                            if (s.n_segments > n_segments_reset) s.n_segments = 0;
-                            s.filter_state = 0;
-                            m = 2;
-                        }
-                }
-            mode[i] = m;
-            s.n_segments++;
-        }
-    *st = s;  // last_out / (Notch) z0 are completed by the apply kernel
-}
-
-// the affine map of sample n (output index): out = a + b * out_prev
-__device__ __forceinline__ void sample_map(const float2* __restrict__ x, unsigned long long n, int length, const unsigned char* __restrict__ mode,
-    const float2* __restrict__ z0_seg, bool lite, float p, float2& a, float2& b, float2* z_out = nullptr)
-{
-    const unsigned long long s = n / length;
-    const unsigned char m = mode[s];
-    const float2 cur = x[n + 1], prev = x[n];
-    if ((m & 0x7f) != 1)
-        {
-            a = cur;
-            b = make_float2(0.0f, 0.0f);
+            *need_floor = 1;  // the host sized this call without the floor values: it repeats the call with them (the state was not written yet)
             return;
         }
-    const float2 z = lite ? z0_seg[s] : phase_step(cur, prev);
-    if (z_out) *z_out = z;
-    a = csub(cur, cmul_ref(z, prev));                                 // in[n] - z0 in[n-1]
-    b = cmul_ref(make_float2(p, 0.0f), z);                            // p_c_factor_ * z_0_ (complex product as the block forms it)
-    if ((m & 0x80) && (n - s * length == 0)) b = make_float2(0.0f, 0.0f);  // the filter engages: last_out_ = 0
+    *st = s;  // last_out / (Notch) z0 are completed by the apply kernel
 }
 
 __global__ __launch_bounds__(NF_THREADS) void notch_compose_kernel(const float2* __restrict__ x, unsigned long long n_total, int length,
@@ -324,8 +162,7 @@ extern "C"
         p->n_segments_reset = n_segments_reset;
         p->n_segments_coeff = n_segments_coeff;
         p->p_c_factor = p_c_factor;
-        // notch.cc:54-55: thres_ = quantile(complement(chi_squared(2 * length), pfa)) = 2 * gamma_p_inv(length, 1 - pfa), in float
-        p->thres = static_cast<float>(2.0 * gsh::gamma_p_inv(static_cast<double>(length), 1.0 - static_cast<double>(pfa)));
+        p->thres = gsh::nf_threshold(pfa, length);  // notch.cc:54-55
         auto fail = [&](hipError_t e, const char* what) {
             gsh::hip_fail(e, what, __FILE__, __LINE__);
             gsh_notch_destroy(p);
@@ -396,10 +233,10 @@ extern "C"
         // the floor values cost a length-point DFT per segment: formed only when this call can reach an estimating segment (the state machine asks for a
         // repeat with them in the one case the shadow cannot foresee: the filter disengaging inside the call while the counter is still below n_segments_est)
         const gsh_notch::State& h = p->h_state;
-        bool with_floor = (h.n_segments < p->n_segments_est) || (static_cast<uint64_t>(h.n_segments) + n_seg > static_cast<uint64_t>(p->n_segments_reset));
-        const int seg_per_wg = std::max(1, 2048 / p->length);
+        bool with_floor = gsh::nf_needs_floor(h.n_segments, n_seg, p->n_segments_est, p->n_segments_reset);
+        const int seg_per_wg = gsh::nf_seg_per_wg(p->length);
         const unsigned blocks_s = static_cast<unsigned>((n_seg + seg_per_wg - 1) / seg_per_wg);
-        const size_t lds = sizeof(float2) * p->length + (sizeof(float2) + sizeof(float)) * static_cast<size_t>(seg_per_wg) * p->length;
+        const size_t lds = gsh::nf_segment_lds(p->length);
         for (int attempt = 0; attempt < 2; attempt++)
             {
                 GSH_HIP(hipMemsetAsync(d_need, 0, sizeof(int), p->stream));

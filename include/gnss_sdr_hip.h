@@ -553,6 +553,7 @@ extern "C"
      * stream is cut into pushes does not matter.  Only the filter outputs the resampler keeps are formed.  The handle owns its device staging
      * and the converted history (n_taps - 1 samples) between pushes; all counts are integers computed on the host, a push reads nothing back.
      * Pulse_Blanking_Filter is an optional stage between the filter and the resampler (gsh_cond_set_blanking below).
+     * So are the notch filters, in this chain's own cut-invariant form with all state on the device (gsh_cond_set_notch below).
      * Not stages of this chain (they stay loose calls): Notch_Filter, Notch_Filter_Lite (gsh_notch_*: a one-sample advance and a state the host
      * shadows); a fan-out of several filters into several rings; stream groups; the cshort / cbyte outputs of the xlating adapter
      * (freq_xlating_fir_filter.cc:136-160). */
@@ -638,6 +639,66 @@ extern "C"
     int gsh_cond_plan_blanked(const gsh_cond_conf* conf, const gsh_cond_blanking* blanking, uint64_t n_in_total, uint64_t* n_out_total);
     /* waits for the handle's queued pushes, then reads the state.  GSH_ERR_STATE on a handle without the stage. */
     int gsh_cond_blanking_state(gsh_cond_t* h, struct gsh_cond_blanking_state* state);
+    /* ---- the notch filters as a stage of the conditioner's push (Notch_Filter: notch_cc.cc:72-118; Notch_Filter_Lite: notch_lite_cc.cc:81-136),
+     * between the filter and the resampler like the blanking stage.
+     * Streams.  With y[0], y[1], ... the filter-output stream of the chain above (the decoded samples themselves when n_taps = 0), the stage forms
+     * the notch output stream w[k], k = 0, 1, ...: w[k] is the mitigated y[k + 1] with y[k] as its previous sample -- the blocks' one-sample
+     * advance (notch_cc.cc:72 `in++`, NotchLite's history item); y[0] is only ever a "sample in front".
+     * Segments.  w is tiled into segments of `length` samples from w[0] on; segment s needs y[1 + s L .. (s + 1) L].  After M >= 1 filter outputs
+     * S = floor((M - 1) / L) segments are decided and W' = S L notch outputs exist (the block's loop condition (index_out + length_) <
+     * noutput_items over the whole stream); the resampler gathers from w with the same m(j), and the ring has every j with m(j) < W'.  A trailing
+     * partial segment waits for the next push; it is never flushed.
+     * Per segment the state machine, the energy, the spectral noise floor, NotchLite's z0 and the per-sample map out = a + b out_prev are those of
+     * gsh_notch_process_device (one text, csrc/notch_filter.h); the energy sum's rotation is keyed to the segment's absolute index, so its bits are
+     * those of one call over the whole stream.
+     * The recurrence is evaluated as gsh_notch_process_device evaluates it within a call: chunks of 128 notch outputs, aligned to the absolute index
+     * (chunk c = w[128 c .. 128 c + 127]), one composite (B, A) per chunk, a sequential carry chain over the chunks, each chunk replayed from its
+     * carry.  The carry handed from push to push is the composite carry at the start of the open chunk, never a replayed output; a chunk that the
+     * push's last decided segment cuts is replayed from its carry up to that segment now, and the next push forms it again from its start and writes
+     * only the new outputs.  Between pushes the handle therefore keeps, in device memory: the filter outputs from y[128 c0] on, c0 = floor(W' / 128)
+     * (at most 128 + length + 1 samples), the modes (NotchLite: and coefficients) of the decided segments that overlap the open chunk (at most 65),
+     * the carry of chunk c0, and the state-machine state.
+     * Invariant: the ring after any sequence of pushes equals, index for index and bit for bit, what the loose chain gives for the concatenated
+     * input with one call per stage: gsh_convert_samples_device / gsh_unpack_device -> gsh_fir_process_device -> one gsh_notch_process_device over
+     * all M filter outputs -> gsh_direct_resample_device.  Where the pushes cut the stream does not matter.  gsh_cond_notch_state equals
+     * gsh_notch_get_state after that one call in noise_pow_est, n_segments, filter_state, n_segments_coeff and, for NotchLite, z0.  (The loose call's
+     * last_out and Notch's per-sample z0 depend on where its last chunk falls: they are not reported.  Several loose calls over the same stream do
+     * not give these bits: each starts its chunks anew and hands on a replayed output.)
+     * A push reads nothing back: no shadow state, no retry.  Whether the noise-floor values (a length-point DFT per segment) are formed is decided
+     * on the device from the state at the start of the push, by the condition gsh_notch_process_device evaluates on its shadow; the decision never
+     * lacks a value it needs, and the bits do not depend on it.
+     * One mitigation stage per handle: gsh_cond_set_notch while blanking is on, and gsh_cond_set_blanking (not NULL) while the notch stage is on,
+     * return GSH_ERR_STATE. */
+    typedef struct
+    {
+        float pfa;                /* in (0, 1) */
+        float p_c_factor;         /* finite */
+        int32_t length;           /* 2..1024 samples per segment */
+        int32_t n_segments_est;   /* >= 0 */
+        int32_t n_segments_reset; /* >= 0 */
+        int32_t n_segments_coeff; /* 0: Notch; >= 1: NotchLite, one coefficient per that many filtered segments */
+    } gsh_cond_notch;
+    struct gsh_cond_notch_state /* a struct tag: the entry point that fills it has the same name */
+    {
+        float thres;              /* gsh_notch_threshold */
+        float noise_pow_est;      /* as gsh_notch_get_state */
+        int32_t n_segments;
+        int32_t filter_state;
+        int32_t n_segments_coeff;
+        int32_t reserved;         /* 0 */
+        float z0[2];              /* NotchLite's coefficient; (0, 0) for Notch */
+        uint64_t n_decided;       /* segments decided since the handle was created */
+        uint64_t n_filtered;      /* ... and those of them that went through the recurrence */
+    };
+    /* Allowed until the handle's first push (GSH_ERR_STATE afterwards, and while the blanking stage is on); GSH_ERR_INVALID with a message for
+     * values outside gsh_notch_create's ranges, before any device is touched.  NULL turns the stage off again.  The push entry points, _position,
+     * _bind and _time_push keep their rules (at most 2^32 filter outputs per push, as with blanking; _time_push changes neither the ring nor any
+     * carried state); a push that completes no segment returns *n_out = 0. */
+    int gsh_cond_set_notch(gsh_cond_t* h, const gsh_cond_notch* notch);
+    /* gsh_cond_plan for a chain with the stage (NULL: without it); no GPU */
+    int gsh_cond_plan_notched(const gsh_cond_conf* conf, const gsh_cond_notch* notch, uint64_t n_in_total, uint64_t* n_out_total);
+    /* waits for the handle's queued pushes, then reads the state.  GSH_ERR_STATE on a handle without the stage. */
+    int gsh_cond_notch_state(gsh_cond_t* h, struct gsh_cond_notch_state* state);
     /* ---- signal generator: synthetic GNSS scenarios made on the device (Signal_Generator: src/algorithms/signal_generator/adapters/
      * signal_generator.cc over gnuradio_blocks/signal_generator_c.h / .cc = sg.cc), into a caller's device buffer or straight into a ring.
      * Table-driven.  A generator holds n_sats <= GSH_GEN_MAX_SATS satellites; a satellite is two complex64 tables A and B of `period` samples
