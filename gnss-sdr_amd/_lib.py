@@ -258,6 +258,8 @@ _I8 = C.POINTER(C.c_int8)
 SYMBOLS = {
     "gsh_abi_version": (C.c_int, []),
     "gsh_device_count": (C.c_int, []),
+    "gsh_mcorr_walk_capacity": (C.c_int, []),
+    "gsh_mcorr_walk_launches": (C.c_uint64, []),
     "gsh_probe_read_bandwidth": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "gsh_last_error": (C.c_char_p, []),
     "gsh_device_name": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t]),

@@ -248,6 +248,15 @@ struct JobCtx
     // (fac_table_fill below) -- null: every lane evaluates its own two transcendentals (run_segment_packed)
     const float2* fac_tab{nullptr};
 };
+// The thread index as run_segment and run_segment_packed read it: threadIdx.x -- unless the kernel runs them inside a loop over jobs (multicorrelator.hip, the
+// walk).  There the context carries a copy the compiler cannot see through, so that nothing derived from it -- lane offsets, LDS addresses, the lanes' sample
+// numbers, in every inlined flavour of the body -- is hoisted out of that loop and held in VGPRs across all of it.
+struct JobCtxLooped : JobCtx
+{
+    int tid;
+};
+__device__ __forceinline__ int ctx_tid(const JobCtx&) { return threadIdx.x; }
+__device__ __forceinline__ int ctx_tid(const JobCtxLooped& c) { return c.tid; }
 // factor table of the batched kernel: the seed of lane tid at re-seed r is A[r] * (WH[tid / 32] * B[tid % 32])
 //   = exp(-j (rem + (n_first + 2 PPC NCH RESEED r) step)) * exp(-j 64 (tid / 32) step) * exp(-j 2 (tid % 32) step)
 // 64 entries, one per lane of the filling wave: each evaluated ONCE per job and work-group instead of two evaluations per lane of every wave
@@ -892,8 +901,8 @@ __device__ __forceinline__ void paired_accumulate(const PairedCodes& d, v2f y0, 
 // accumulator; the fold at the end is gone.  24 accumulator registers become 6, which is what lets a 1 024-thread work-group (128 VGPRs) run TWO chunks per
 // trip: the per-trip overhead (phasor step, index step, loop control, edge tests, the wait for the look-ups) is paid once per four samples instead of once per two.
 // HALF (round 7): the paired trips take all three taps from the prompt chain and the doubled table (packed_trip); the caller vouches for shifts of exactly -0.5 / 0 / +0.5
-template <int NT, bool ZP, bool AUX, int NCH, int PF, bool DER = false, bool KC = false, bool MRG = false, bool HALF = false>
-__device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2* __restrict__ base, const float* __restrict__ tab,
+template <int NT, bool ZP, bool AUX, int NCH, int PF, bool DER = false, bool KC = false, bool MRG = false, bool HALF = false, typename Ctx = JobCtx>
+__device__ __forceinline__ void run_segment_packed(const Ctx& c, const float2* __restrict__ base, const float* __restrict__ tab,
     const float (&sh)[NT], float2 (&acc)[NT], float2* acc_aux)
 {
     static_assert(NCH == 1 || NCH == 2, "one or two chunks per trip");
@@ -901,7 +910,7 @@ __device__ __forceinline__ void run_segment_packed(const JobCtx& c, const float2
     constexpr int PPC = MC_PAIRS_PER_CHUNK;
     constexpr int RESEED = packed_reseed_trips(NCH);     // trips between exact re-seeds
     constexpr int TBL = 60;                               // re-seed entries per table fill
-    const int tid = threadIdx.x;
+    const int tid = ctx_tid(c);
     const int lane = tid & 63;
     const v2f zero = {0.0f, 0.0f};
     // seed tables (c.seed_tab, the closed-loop kernel): the six reads go out first -- their LDS round trip runs under the scalar set-up below
@@ -1765,8 +1774,8 @@ __device__ __forceinline__ void run_segment_runs(const JobCtx& c, const float2* 
 // KC: the whole code is staged behind a MARGIN-entry guard band (c.k_off == MC_MARGIN) at LDS address 0: look-ups use a constant offset
 // PAIRK: zero-shift-prompt E/P/L jobs read their early tap next to the late one (the caller checked the job: mcorr_pair_eligible, multicorrelator.h)
 // HALFK: and their shifts are exactly -0.5 / 0 / +0.5 chip, the doubled table in front of `tab` (mcorr_half_chip_eligible, multicorrelator.h)
-template <int NT, int MODE, bool WRAP, bool ZP = false, bool AUX = false, bool KC = false, bool PAIRK = false, bool HALFK = false>
-__device__ __forceinline__ void run_segment(const JobCtx& c, const float2* __restrict__ base, const float* __restrict__ tab,
+template <int NT, int MODE, bool WRAP, bool ZP = false, bool AUX = false, bool KC = false, bool PAIRK = false, bool HALFK = false, typename Ctx = JobCtx>
+__device__ __forceinline__ void run_segment(const Ctx& c, const float2* __restrict__ base, const float* __restrict__ tab,
     const float (&sh)[NT], const int (&rot)[NT], float2 (&acc)[NT], float2* acc_aux = nullptr)
 {
 #if GSH_MC_PACKED
@@ -1804,7 +1813,7 @@ __device__ __forceinline__ void run_segment(const JobCtx& c, const float2* __res
             return;
         }
 #endif
-    const int tid = threadIdx.x;
+    const int tid = ctx_tid(c);
     const int span = c.n_end - c.n_first;          // samples covered from pair 0's first element
     const int n_pairs = (span + 1) >> 1;           // pairs touching the segment
     const int n_full = span >> 1;                  // leading pairs whose second sample is in range

@@ -36,6 +36,7 @@
 #define mcorr_reduce_partials mcorr_reduce_partials_t128
 #endif
 #include "mcorr_device.h"
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 
@@ -365,6 +366,231 @@ __global__ __launch_bounds__(MC_THREADS, ((NT <= 3 && !AUX) ? GSH_MC_MIN_WAVES :
         }
 }
 
+#ifdef GSH_MC_VARIANT_128
+// The walk (round 11): mcorr_kernel_t128<3, 0, false, false, false, true, true> -- E/P/L, standard mode, whole-code tables, paired taps, half-chip shifts, one
+// work-group per job, no splits -- with its body inside a loop over job slots.  The grid is ONE resident round of work-groups (launch_nt below: G = what the chip
+// holds); work-group lb takes the slots lb, lb + G, lb + 2 G, ... of the launch.  A launch of 12 800 such jobs is otherwise five lock-step rounds of 2 560
+// work-groups, and at the end of each round every wave slot stands empty while its successor is dispatched and goes through the dependent set-up (job record, code
+// length, 13 KB of code image into LDS, barrier, first samples) before its first trip.  Along a walk
+//   * a wave slot is handed over once per launch, not once per job;
+//   * the code image is staged when the job's code slot differs from the one the LDS holds (the job table is epoch-major, channel-minor: with G a multiple of the
+//     channel count a work-group meets the same code slot every time), which does not depend on G: any grid is CORRECT;
+//   * everything else -- factor table, judgement, accumulators, JobCtx, fold, wave sums, the job's own output row -- is the parent's, per job: the same lanes take
+//     the same samples, the same products enter the same sums in the same order, and the outputs are the parent's bit for bit (tests/test_tracking_walk_gpu.py).
+// What keeps the loop at the parent's registers (profiles/ab/r06/chain_kernel.patch learned both):
+//   * the arguments are read per job THROUGH A POINTER into the kernarg segment that is made opaque at the head of every job, not from the by-value parameter: what
+//     the compiler knows to be invariant it keeps in SGPRs across the whole loop, thirty-odd registers the trip loops do not need;
+//   * the job table, the launch list and the code lengths are read through the constant address space (nothing writes them while the kernel runs): scalar loads,
+//     although the loop's own output stores lie between one job's reads and the next one's.
+// Barriers: two per job, as in the parent -- B1 "tables visible", B2 "red written".  No third one between job k's reduction and job k + 1's writes while the code
+// slot stays:
+//   * after B2 only the first wave reads `red` of job k (tid < GSH_MAX_TAPS).  Before B1 of job k + 1 the first wave writes `fac` (the same wave, behind its own
+//     reads, at another address: the layout depends on the code length only, and the slot is the same), and nobody writes the code tables; `red` of job k + 1 is
+//     written after B1 of job k + 1, which the first wave enters only with its reads of job k complete (the barrier's fence waits for them);
+//   * `fac` of job k is read by both waves inside the trips, i.e. before B2 of job k; it is rewritten after B2;
+//   * the code tables are read before B2 of job k and not written at all.
+// When the slot CHANGES the other wave may start to overwrite the tables -- with another code length, at the place of job k's `red` -- while the first wave still
+// sums job k: that path, and only that path, begins with a barrier of its own.
+// The register budget is the parent's, 96 (five waves per SIMD), and tests/test_tracking_walk_resources.py holds the kernel to it.  The bound ASKED of the compiler is
+// four waves: inside the loop over jobs it hoists the constants of every inlined carrier-seed evaluation (four registers) and one constant pair of the half-chip
+// set-up in front of the loop, and held to 96 from the outset it parks that pair in scratch (12 bytes: one store per wave, one load per job -- and a kernel that uses
+// scratch at all); free to take 128 it allocates exactly 96 and spills nothing.
+#ifndef GSH_MC_WALK_MIN_WAVES
+#define GSH_MC_WALK_MIN_WAVES 4
+#endif
+#ifndef GSH_MC_WALK_PRIO
+#define GSH_MC_WALK_PRIO 1  // a walk's issue priority falls with the jobs it has left (below); 0: every wave at the default priority (A/B: profiles/r11_summary.txt)
+#endif
+__global__ __launch_bounds__(MC_THREADS, GSH_MC_WALK_MIN_WAVES) void mcorr_walk_kernel_t128(McorrArgs args_in_kernarg_segment)
+{
+    constexpr int NT = 3;
+    (void)args_in_kernarg_segment;
+    typedef const __attribute__((address_space(4))) McorrArgs* kernarg_ptr;
+    typedef const __attribute__((address_space(4))) gsh_corr_job* job_ptr;
+    typedef const __attribute__((address_space(4))) int* const_int_ptr;
+    typedef const __attribute__((address_space(3))) float* lds_float_ptr;
+    extern __shared__ __align__(16) float lds[];
+    int staged = -1;  // the code slot whose image the LDS holds
+    int tid = threadIdx.x;
+    for (unsigned slot = xcd_remap(blockIdx.x, gridDim.x);; slot += gridDim.x)
+        {
+            kernarg_ptr ap = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ap));
+#define a (*ap)
+            if (slot >= static_cast<unsigned>(a.n_launch)) break;
+#if GSH_MC_WALK_PRIO
+            {
+                // A SIMD issues by priority, then by age: among five resident waves of equal priority the oldest wins every tie, for the whole launch, and finishes its
+                // walk long before the youngest -- the slots it leaves stay empty (one resident round: nothing is waiting for them) and the stragglers run on a
+                // half-empty SIMD.  The jobs a walk still has in front of it are its priority: a wave that is ahead yields to those behind it.
+                const unsigned left = (static_cast<unsigned>(a.n_launch) - 1u - slot) / gridDim.x;
+                if (left >= 3u)
+                    __builtin_amdgcn_s_setprio(3);
+                else if (left == 2u)
+                    __builtin_amdgcn_s_setprio(2);
+                else if (left == 1u)
+                    __builtin_amdgcn_s_setprio(1);
+                else
+                    __builtin_amdgcn_s_setprio(0);
+            }
+#endif
+            asm volatile("" : "+v"(tid));  // (opaque, in place: no lane arithmetic derived from it is hoisted out of the loop and kept across all of it)
+            const int job = a.job_list ? ((const_int_ptr)a.job_list)[slot] : static_cast<int>(slot);
+            const job_ptr Jp = (job_ptr)a.jobs + job;
+            const int code_slot = Jp->code_slot, n_taps = Jp->n_taps;
+            const float jsh[NT] = {Jp->shifts_chips[0], Jp->shifts_chips[1], Jp->shifts_chips[2]};
+
+            JobCtxLooped c;
+            c.n_total = Jp->n_samples;
+            c.code_len = ((const_int_ptr)a.code_lens)[code_slot];
+            c.rem_carr = Jp->rem_carr_phase_rad;
+            c.phase_step = Jp->phase_step_rad;
+            c.phase_rate = Jp->phase_rate_step_rad;
+            c.rem_code = Jp->rem_code_phase_chips;
+            c.code_step = Jp->code_phase_step_chips;
+            c.code_rate = Jp->code_phase_rate_step_chips;
+            c.packed = a.packed != 0;
+            c.runs = false;
+            c.tid = tid;
+
+            // ---- the window (splits == 1: the whole of it)
+            c.n_begin = 0;
+            c.n_end = c.n_total;
+            unsigned long long win0 = Jp->sample_offset + a.sample_base;
+            if (a.ring_capacity) win0 %= a.ring_capacity;
+            const int odd = static_cast<int>(win0 & 1ULL);
+            c.n_first = -odd;
+            const float2* __restrict__ base = a.stream + (win0 - static_cast<unsigned long long>(odd));  // 16-byte aligned
+
+            // unused slots repeat the last real shift, as in mcorr_kernel (a job with fewer than three taps is a misfit here: its shifts are never used)
+            const int last_tap = max(n_taps, 1) - 1;
+            float sh[NT];
+            int rot[NT];
+            sh[0] = jsh[0];
+            sh[1] = last_tap >= 1 ? jsh[1] : jsh[0];
+            sh[2] = last_tap >= 2 ? jsh[2] : sh[1];
+#pragma unroll
+            for (int t = 0; t < NT; t++) rot[t] = 0;
+
+            int lo = 0, hi = -1;
+            if (c.n_end > c.n_begin)
+                {
+                    const float smin = fminf(fminf(sh[0], sh[1]), sh[2]), smax = fmaxf(fmaxf(sh[0], sh[1]), sh[2]);
+                    lo = raw_chip_std(__fmul_rn(c.code_step, static_cast<float>(c.n_begin)), smin, c.rem_code);
+                    hi = raw_chip_std(__fmul_rn(c.code_step, static_cast<float>(c.n_end - 1)), smax, c.rem_code);
+                }
+
+            // ---- the code image, when the LDS does not hold it already (mcorr_kernel, HALF, explains the copy)
+            float* const tab = lds + MC_HALF_WORDS;
+            bool misfit = false;
+            int lds_floats;
+            const bool pair_ok = gsh::mcorr_half_chip_eligible(n_taps, jsh, c.code_step, Jp->high_dyn, c.code_len);
+            if (a.window_floats > 0 || !pair_ok || reinterpret_cast<size_t>((lds_float_ptr)lds) != 0)
+                {
+                    misfit = (c.n_end > c.n_begin);  // cannot happen: the launcher picks this kernel from the same fields; reported as NaN if it does
+                    lds_floats = a.window_floats > 0 ? a.window_floats : c.code_len + 2 * MC_MARGIN;
+                    if (staged >= 0) __syncthreads();  // `red` of this job lies inside the tables: the first wave may still sum the job before
+                    staged = -1;
+                }
+            else
+                {
+                    const int tab_len = c.code_len + 2 * MC_MARGIN;
+                    if (code_slot != staged)  // uniform over the work-group
+                        {
+                            if (staged >= 0) __syncthreads();  // (see above: the first wave may still read `red` of the job before, where this table will lie)
+                            const int rows_dbl = (2 * tab_len + 3) >> 2, rows = rows_dbl + ((tab_len + 3) >> 2);
+                            const char* const image = reinterpret_cast<const char*>(a.code_images + static_cast<size_t>(code_slot) * MCORR_HALF_IMAGE_WORDS);
+                            constexpr int PER_THREAD = (MCORR_HALF_IMAGE_WORDS / 4 + MC_THREADS - 1) / MC_THREADS;
+                            const unsigned last = 16u * static_cast<unsigned>(rows - 1), end_dbl = 16u * static_cast<unsigned>(rows_dbl);
+                            const unsigned skip = 4u * MC_HALF_WORDS - end_dbl;  // from the doubled table's last row to the plain table's first
+                            unsigned at[PER_THREAD];
+                            float4 row[PER_THREAD];
+                            typedef float row_t __attribute__((ext_vector_type(4)));
+                            typedef __attribute__((address_space(3))) row_t* lds_row_ptr;
+#pragma unroll
+                            for (int i = 0; i < PER_THREAD; i++)
+                                {
+                                    const unsigned r = min(16u * static_cast<unsigned>(tid + i * MC_THREADS), last);
+                                    at[i] = r < end_dbl ? r : r + skip;
+                                    row[i] = *reinterpret_cast<const float4*>(image + at[i]);
+                                }
+#pragma unroll
+                            for (int i = 0; i < PER_THREAD; i++) *reinterpret_cast<lds_row_ptr>(at[i]) = (row_t){row[i].x, row[i].y, row[i].z, row[i].w};
+                            staged = code_slot;
+                        }
+                    lds_floats = tab_len + MC_HALF_WORDS;
+                }
+            float2* red = reinterpret_cast<float2*>(lds + ((lds_floats + 3) & ~3));
+            float2* const fac = red + MC_WAVES * GSH_MAX_TAPS;
+            if (a.packed != 0 && a.fac != 0)
+                {
+                    if ((tid >> 6) == 0) fac_table_fill<2>(fac, c.phase_step, c.rem_carr, c.n_first, tid);
+                    c.fac_tab = fac;
+                }
+
+            float2 acc[NT];
+#pragma unroll
+            for (int t = 0; t < NT; t++) acc[t] = make_float2(0.0f, 0.0f);
+            float2 acc_aux = make_float2(0.0f, 0.0f);
+
+            __syncthreads();  // B1: code tables and factor table visible
+
+            if (misfit)
+                {
+#pragma unroll
+                    for (int t = 0; t < NT; t++) acc[t] = make_float2(__builtin_nanf(""), __builtin_nanf(""));
+                }
+            else if (c.n_end > c.n_begin)
+                {
+                    const bool fast = (c.code_step >= 0.0f) && (lo >= -MC_MARGIN) && (hi < c.code_len + MC_MARGIN) && (c.code_len >= MC_MARGIN);
+                    const bool zp = (NT == n_taps) && (sh[NT / 2] == 0.0f) && (c.n_total < (1 << 24));
+                    if (fast && zp)
+                        run_segment<NT, 0, false, true, false, true, true, true>(c, base, tab, sh, rot, acc, &acc_aux);
+                    else if (fast)
+                        run_segment<NT, 0, false, false, false, false>(c, base, tab, sh, rot, acc, &acc_aux);
+                    else
+                        run_segment<NT, 0, true, false, false>(c, base, tab, sh, rot, acc, &acc_aux);
+                }
+
+            // ---- integrate-and-dump, as in mcorr_kernel
+            {
+                float sums[2 * NT];
+#pragma unroll
+                for (int t = 0; t < NT; t++)
+                    {
+                        sums[2 * t] = acc[t].x;
+                        sums[2 * t + 1] = acc[t].y;
+                    }
+                wave_scan_incl_n(sums);
+#pragma unroll
+                for (int t = 0; t < NT; t++) acc[t] = make_float2(sums[2 * t], sums[2 * t + 1]);
+            }
+            const int wave = tid >> 6;
+            if ((tid & 63) == 63)
+                {
+#pragma unroll
+                    for (int t = 0; t < NT; t++) red[wave * GSH_MAX_TAPS + t] = acc[t];
+                }
+            __syncthreads();  // B2: `red` written
+            if (tid < GSH_MAX_TAPS)
+                {
+                    float2 s = make_float2(0.0f, 0.0f);
+                    if (tid < NT && tid < n_taps)
+                        {
+#pragma unroll
+                            for (int w = 0; w < MC_WAVES; w++)
+                                {
+                                    s.x += red[w * GSH_MAX_TAPS + tid].x;
+                                    s.y += red[w * GSH_MAX_TAPS + tid].y;
+                                }
+                        }
+                    a.out[static_cast<size_t>(job) * GSH_MAX_TAPS + tid] = s;
+                }
+#undef a
+        }
+}
+#endif  // GSH_MC_VARIANT_128
+
 // sums the per-split partials of each job in split order (deterministic)
 __global__ __launch_bounds__(256) void mcorr_reduce_partials(const float2* __restrict__ partials, float2* __restrict__ out, int n_jobs, int splits)
 {
@@ -380,6 +606,53 @@ __global__ __launch_bounds__(256) void mcorr_reduce_partials(const float2* __res
         }
     out[i] = s;
 }
+
+#ifdef GSH_MC_VARIANT_128
+// Work-groups of mcorr_walk_kernel_t128 the current device holds at once (occupancy x compute units, with the most LDS the half-chip flavour ever asks for):
+// asked once per device.  0: the runtime could not say -- no walk.
+int walk_capacity()
+{
+    constexpr int MAX_DEVICES = 64;
+    static std::atomic<int> cached[MAX_DEVICES];  // 0: not asked yet; -1: asked, no answer
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return 0;
+    int v = cached[dev].load(std::memory_order_relaxed);
+    if (v == 0)
+        {
+            const size_t lds_most = static_cast<size_t>(MC_HALF_WORDS) * sizeof(float)
+                                    + ((static_cast<size_t>(MC_HALF_MAX_CODE_LEN) + 2 * MC_MARGIN + 3) & ~static_cast<size_t>(3)) * sizeof(float)
+                                    + (MC_WAVES * GSH_MAX_TAPS + FAC_ENTRIES) * sizeof(float2);
+            int per_cu = 0, cus = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mcorr_walk_kernel_t128, MC_THREADS, lds_most) != hipSuccess
+                || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu <= 0 || cus <= 0)
+                {
+                    (void)hipGetLastError();
+                    v = -1;
+                }
+            else
+                v = per_cu * cus;
+            cached[dev].store(v, std::memory_order_relaxed);
+        }
+    return v > 0 ? v : 0;
+}
+
+// Grid of the walk for a launch that would take mcorr_kernel_t128<3, 0, false, false, false, true, true>; 0: that kernel itself, one work-group per job.
+// GSH_MC_WALK (read once; A/B runs and tests): 0 never walks; a positive number is the grid, whatever the size of the launch; unset, the grid is one resident
+// round of work-groups once the launch holds at least two of them (below that a chip that is not full wants one work-group per job).
+int walk_grid(const McorrArgs& a)
+{
+    static const int forced = [] {
+        const char* e = std::getenv("GSH_MC_WALK");
+        return (e != nullptr && e[0] != '\0') ? std::atoi(e) : -1;
+    }();
+    if (forced == 0 || a.splits != 1 || a.n_launch <= 0) return 0;
+    if (forced > 0) return forced;
+    const int g = walk_capacity();
+    return (g > 0 && static_cast<long long>(a.n_launch) >= 2LL * g) ? g : 0;
+}
+
+std::atomic<unsigned long long> walk_launches{0};  // launches of this process that took the walk (gsh_mcorr_walk_launches)
+#endif
 
 // lds_half: the LDS bytes of the half-chip flavour for this launch's codes (mcorr_lds_bytes_half), 0 when they are too long for it
 template <int NT>
@@ -426,7 +699,18 @@ int launch_nt(const McorrArgs& a, int mode, size_t lds, size_t lds_half, hipStre
                             if (a.window_floats > 0)
                                 hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, true, true>), grid, block, lds, stream, a);
                             else if (a.half && lds_half > 0 && a.code_images != nullptr)
-                                hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, false, true, true>), grid, block, lds_half, stream, a);
+                                {
+#ifdef GSH_MC_VARIANT_128
+                                    const int walk = walk_grid(a);
+                                    if (walk > 0)
+                                        {
+                                            hipLaunchKernelGGL(mcorr_walk_kernel_t128, dim3(static_cast<unsigned>(walk)), block, lds_half, stream, a);
+                                            walk_launches.fetch_add(1, std::memory_order_relaxed);
+                                        }
+                                    else
+#endif
+                                        hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, false, true, true>), grid, block, lds_half, stream, a);
+                                }
                             else
                                 hipLaunchKernelGGL((mcorr_kernel<NT, 0, false, false, false, true>), grid, block, lds, stream, a);
                             break;
@@ -624,3 +908,11 @@ int mcorr_launch_classes(const McorrArgs& args, const McorrClassPlan& plan, int 
     return GSH_OK;
 }
 }  // namespace gsh
+
+#ifdef GSH_MC_VARIANT_128
+extern "C"
+{
+    int gsh_mcorr_walk_capacity(void) { return gsh::walk_capacity(); }
+    uint64_t gsh_mcorr_walk_launches(void) { return gsh::walk_launches.load(std::memory_order_relaxed); }
+}
+#endif

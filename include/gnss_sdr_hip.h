@@ -146,6 +146,11 @@ extern "C"
     /* work-groups per job used by the next launches (1 = throughput mode; >1 spreads one epoch
      * over more CUs for latency-bound closed-loop use).  0 = choose automatically. */
     int gsh_bank_set_splits(gsh_bank_t* b, int splits);
+    /* diagnostics of the E/P/L correlator's walk (one resident round of work-groups, each walking several jobs: csrc/multicorrelator.hip):
+     * the work-groups of that kernel the calling thread's current device holds at once (0: unknown, no launch walks of its own accord),
+     * and how many launches of this process have taken the walk so far. */
+    int gsh_mcorr_walk_capacity(void);
+    uint64_t gsh_mcorr_walk_launches(void);
     /* an offset (in samples) added to every job's sample_offset at launch time: a job table uploaded once -- window positions relative to
      * the start of a block -- serves block after block of a long stream or of a ring (positions are taken modulo the ring's capacity)
      * without being re-staged and re-uploaded every time.  The caller keeps the shifted windows inside the stream / resident in the ring. */
