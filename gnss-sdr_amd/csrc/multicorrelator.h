@@ -29,6 +29,7 @@ constexpr int MCORR_MARGIN = 32;                                                
 constexpr int MCORR_HALF_WORDS = 2 * (MCORR_HALF_MAX_CODE_LEN + 2 * MCORR_MARGIN);                // the doubled table's room
 constexpr int MCORR_HALF_IMAGE_WORDS = MCORR_HALF_WORDS + MCORR_HALF_MAX_CODE_LEN + 2 * MCORR_MARGIN;  // 3 264 words, a whole number of 16-byte rows
 static_assert(MCORR_HALF_WORDS % 4 == 0 && MCORR_HALF_IMAGE_WORDS % 4 == 0, "the image is copied in 16-byte rows");
+constexpr int MCORR_FAC_ENTRIES = 64;  // float2 entries of a work-group's carrier-seed factor table, behind its wave sums in the LDS (mcorr_device.h fac_table_fill)
 inline void mcorr_build_half_image(const float* code, int code_len, float* image)
 {
     for (int i = 0; i < MCORR_HALF_IMAGE_WORDS; i++) image[i] = 0.0f;
@@ -85,18 +86,20 @@ struct McorrClassPlan
     bool aux[4];
 };
 int mcorr_launch_classes(const McorrArgs& args, const McorrClassPlan& plan, int mode, int max_code_len, hipStream_t stream);
-// the same through the 128-thread kernels (csrc/multicorrelator_t128.hip); mcorr_launch / mcorr_launch_classes choose, callers do not
-int mcorr_launch_t128(const McorrArgs& args, int max_taps, int mode, int max_code_len, hipStream_t stream);
-int mcorr_launch_classes_t128(const McorrArgs& args, const McorrClassPlan& plan, int mode, int max_code_len, hipStream_t stream);
+// The two-wave kernels' only entry (csrc/multicorrelator_t128.hip): one E/P/L launch in the standard mode with whole-code tables and no fused jobs, i.e. what
+// use_128() of csrc/multicorrelator.hip admits -- mcorr_launch / mcorr_launch_classes choose, callers do not.  lds / lds_half: mcorr_lds_bytes /
+// mcorr_lds_bytes_half of the launch's longest code at two waves.  It launches the kernel and nothing else: the partials are summed by its caller.
+int mcorr_launch_epl_t128(const McorrArgs& args, size_t lds, size_t lds_half, hipStream_t stream);
 
-// dynamic LDS bytes the kernel needs for a code of max_code_len samples
-size_t mcorr_lds_bytes(int max_code_len);
+// dynamic LDS bytes a work-group of `waves` waves needs for a code of max_code_len samples (every caller but the launcher means the four-wave kernels)
+constexpr int MCORR_WAVES = 4;
+size_t mcorr_lds_bytes(int max_code_len, int waves = MCORR_WAVES);
 // the same for the half-chip flavour of the E/P/L kernels (a doubled table in front); 0: the code is too long for that flavour
-size_t mcorr_lds_bytes_half(int max_code_len);
+size_t mcorr_lds_bytes_half(int max_code_len, int waves = MCORR_WAVES);
 // the same when only `window_floats` code samples are staged per work-group
-size_t mcorr_lds_bytes_window(int window_floats);
+size_t mcorr_lds_bytes_window(int window_floats, int waves = MCORR_WAVES);
 // LDS bytes with room for the fused correlator's second code table (aux != nullptr)
-size_t mcorr_lds_bytes_fused(int max_code_len, int window_floats);
+size_t mcorr_lds_bytes_fused(int max_code_len, int window_floats, int waves = MCORR_WAVES);
 }  // namespace gsh
 
 #endif

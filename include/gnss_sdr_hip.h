@@ -146,7 +146,7 @@ extern "C"
     /* work-groups per job used by the next launches (1 = throughput mode; >1 spreads one epoch
      * over more CUs for latency-bound closed-loop use).  0 = choose automatically. */
     int gsh_bank_set_splits(gsh_bank_t* b, int splits);
-    /* diagnostics of the E/P/L correlator's walk (one resident round of work-groups, each walking several jobs: csrc/multicorrelator.hip):
+    /* diagnostics of the E/P/L correlator's walk (one resident round of work-groups, each walking several jobs: csrc/mcorr_kernels.h):
      * the work-groups of that kernel the calling thread's current device holds at once (0: unknown, no launch walks of its own accord),
      * and how many launches of this process have taken the walk so far. */
     int gsh_mcorr_walk_capacity(void);

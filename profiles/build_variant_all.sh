@@ -1,5 +1,5 @@
 #!/bin/bash
-# build/variants/lib_<tag>.so = the library with EVERY translation unit that includes csrc/mcorr_device.h recompiled under extra -D flags
+# build/variants/lib_<tag>.so = the library with EVERY translation unit that includes csrc/mcorr_device.h, directly or through csrc/mcorr_kernels.h, recompiled under extra -D flags
 # usage: bash profiles/build_variant_all.sh rtn:-DGSH_MC_RTN_FLOOR=1 ...
 set -e
 R=$(cd $(dirname $0)/.. && pwd); P=$R/gnss-sdr_amd
@@ -10,7 +10,7 @@ for spec in "$@"; do
   objs=""
   for o in $P/_build/*.o; do
     b=$(basename $o .o)
-    if grep -q "mcorr_device.h\|multicorrelator.hip" $P/csrc/$b.hip; then
+    if grep -q "mcorr_device.h\|mcorr_kernels.h" $P/csrc/$b.hip; then
       ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-function -I$R/include -I$P/csrc $defs -c $P/csrc/$b.hip -o $R/build/variants/${b}_$tag.o 2>/dev/null ) &
       objs="$objs $R/build/variants/${b}_$tag.o"
     else

@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel-tuning helper: build/variants/lib_<tag>.so = the library with multicorrelator.hip and multicorrelator_t128.hip (the same kernels at 128 threads: the headline
+# kernel-tuning helper: build/variants/lib_<tag>.so = the library with multicorrelator.hip and multicorrelator_t128.hip (the kernel text of csrc/mcorr_kernels.h at 256 and at 128 threads: the headline
 # kernel of bench.py) recompiled under extra -D flags
 # usage: bash profiles/build_variants.sh t64:-DGSH_MC_THREADS=64 queue1:-DGSH_MC_PAIR_QUEUE=1 nobarrier:-DGSH_MC_PAIR_QUEUE=2,-DGSH_MC_PAIR_BARRIER=0 ...
 set -e
