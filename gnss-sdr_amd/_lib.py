@@ -169,6 +169,27 @@ class ArrayFormat(C.Structure):
     ]
 
 
+class BeamAdapt(C.Structure):
+    """gsh_beam_adapt (1048 bytes): the adaptive mode of a beamformer (array.Beamformer.set_adaptive builds it)."""
+    _fields_ = [
+        ("forgetting", C.c_double),
+        ("loading_rel", C.c_double),
+        ("loading_abs", C.c_double),
+        ("constraint_iq", C.c_double * 2 * GSH_ARRAY_MAX_ANTENNAS * GSH_ARRAY_MAX_BEAMS),   # [beam][antenna][re, im]
+    ]
+
+
+class BeamAdaptState(C.Structure):
+    """struct gsh_beam_adapt_state (1560 bytes): what gsh_adaptive_beam_state reads back (array.Beamformer.adaptive_state)."""
+    _fields_ = [
+        ("blocks", C.c_uint64),
+        ("failures", C.c_uint64),
+        ("delta", C.c_double),
+        ("r_acc_iq", C.c_double * (GSH_ARRAY_MAX_ANTENNAS * GSH_ARRAY_MAX_ANTENNAS * 2)),
+        ("w_iq", C.c_float * (GSH_ARRAY_MAX_BEAMS * GSH_ARRAY_MAX_ANTENNAS * 2)),
+    ]
+
+
 class CondConf(C.Structure):
     """gsh_cond_conf (96 bytes): the signal conditioner's chain (conditioner.SignalConditioner builds it)."""
     _fields_ = [
@@ -361,6 +382,8 @@ SYMBOLS = {
     "gsh_beam_covariance": (C.c_int, [_P, C.POINTER(_P), C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "gsh_beam_covariance_device": (C.c_int, [_P, C.POINTER(_P), C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "gsh_beam_time_process": (C.c_int, [_P, C.c_uint64, C.c_int, _F]),
+    "gsh_adaptive_beam_set": (C.c_int, [_P, C.POINTER(BeamAdapt)]),
+    "gsh_adaptive_beam_state": (C.c_int, [_P, C.POINTER(BeamAdaptState)]),
     "gsh_fir_create": (C.c_int, [C.c_int, _F, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_P)]),
     "gsh_fir_destroy": (None, [_P]),
     "gsh_fir_process_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64), _P]),

@@ -73,6 +73,42 @@ class Beamformer:
         check(self._lib.gsh_beam_get_weights(self._h, fptr(out)))
         return out
 
+    def set_adaptive(self, steering=None, reference=None, forgetting: float = 0.0, loading_rel: float = 0.0, loading_abs: float = 0.0) -> None:
+        """gsh_adaptive_beam_set: from the next call on, every process_device / push / push_device forms the block's covariance, accumulates it
+        (R_acc <- forgetting * R_acc + R_block), solves for every beam's weights and forms the beams with them, all on the device on the call's stream.
+        steering: one vector [n_antennas] for every beam or one per beam [n_beams, n_antennas] (MVDR: w = conj(R^-1 s / (s^H R^-1 s)));
+        reference: an element index, or one per beam (power inversion: that element's weight is held at 1).  The loading added to R_acc's diagonal is
+        loading_rel * trace(R_acc) / n_antennas + loading_abs.  set_adaptive(None) turns the mode off: the weights of set_weights are in force again."""
+        if steering is None and reference is None:
+            check(self._lib.gsh_adaptive_beam_set(self._h, None))
+            return
+        if steering is not None and reference is not None:
+            raise ValueError("an adaptive beam is constrained by a steering vector or by a reference element, not both")
+        A = self.fmt.n_antennas
+        c = np.zeros((GSH_ARRAY_MAX_BEAMS, GSH_ARRAY_MAX_ANTENNAS), np.complex128)
+        if steering is not None:
+            s = np.asarray(steering, np.complex128)
+            if s.shape not in ((A,), (self.n_beams, A)):
+                raise ValueError(f"steering of shape {s.shape} for {self.n_beams} beams of {A} antennas")
+            c[:self.n_beams, :A] = s
+        else:
+            ref = np.broadcast_to(np.asarray(reference, np.int64), (self.n_beams,))
+            if np.any(ref < 0) or np.any(ref >= A):
+                raise ValueError(f"reference element {reference} of {A} antennas")
+            c[np.arange(self.n_beams), ref] = 1.0
+        conf = _lib.BeamAdapt(float(forgetting), float(loading_rel), float(loading_abs))
+        C.memmove(conf.constraint_iq, np.ascontiguousarray(c).ctypes.data, c.nbytes)
+        check(self._lib.gsh_adaptive_beam_set(self._h, C.byref(conf)))
+
+    def adaptive_state(self) -> dict:
+        """gsh_adaptive_beam_state (synchronous): blocks, failures, delta, r_acc (complex128 [A, A]) and the weights in force (complex64 [n_beams, A])"""
+        st = _lib.BeamAdaptState()
+        check(self._lib.gsh_adaptive_beam_state(self._h, C.byref(st)))
+        A = self.fmt.n_antennas
+        r = np.frombuffer(st.r_acc_iq, np.float64, 2 * A * A).copy().view(np.complex128).reshape(A, A)
+        w = np.frombuffer(st.w_iq, np.float32, 2 * self.n_beams * A).copy().view(np.complex64).reshape(self.n_beams, A)
+        return dict(blocks=int(st.blocks), failures=int(st.failures), delta=float(st.delta), r_acc=r, weights=w)
+
     def _host_buffers(self, items):
         """planar: a sequence of n_antennas arrays (or one array [n_antennas, ...]); interleaved: one array.  -> (arrays kept alive, pointers, n)"""
         dt = _NP[ITEM_TYPES[self.fmt.item_type]]

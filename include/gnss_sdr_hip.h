@@ -521,6 +521,47 @@ extern "C"
     int gsh_beam_covariance_device(gsh_beam_t* b, const void* const* device_items, uint64_t n, int inverted_spectrum, double* r_iq);
     /* average time of one beam pass over a zero-filled block of n samples in the handle's format, HIP events, as the other gsh_*_time_* calls */
     int gsh_beam_time_process(gsh_beam_t* b, uint64_t n, int reps, float* avg_ms);
+    /* Adaptive mode: the weights of every beam come from the covariance of the blocks themselves, on the device.  On an adaptive handle
+     * gsh_beam_process_device, gsh_beam_push and gsh_beam_push_device queue, on the stream the call works on,
+     *   covariance partials -> final sums (R_block: gsh_beam_covariance_device of the block, bit for bit) -> accumulate and solve -> beam pass
+     * with no read-back and no host synchronisation beyond what the fixed-weight call of the same name does.  The raw block is read twice on the
+     * device and crosses PCIe once.  Arithmetic (the definition; csrc/array_weights.h, FP64, one rounding per operation, no square root, every
+     * sum in ascending index order):
+     *   R_acc <- forgetting * R_acc + R_block                 per real number of the upper triangle; the diagonal's imaginary parts are 0
+     *   delta  = loading_rel * (sum_i Re R_acc[i][i]) / A + loading_abs,   M = R_acc + delta I
+     *   M = L D L^H                                           square-root-free Cholesky, column by column, no pivoting
+     *   per beam, c its constraint vector:  L y = c,  z = y / D,  L^H u = z,  d = sum_i conj(c_i) u_i,  v = u conj(d) / |d|^2
+     *   w = conj(v), each part rounded once to float32        (the block's convention y = sum_a x_a w_a)
+     * c = the steering vector s gives the MVDR weights R^-1 s / (s^H R^-1 s); c = the unit vector of a reference element gives power inversion
+     * (that element's weight is exactly (1, 0)).  The weights a block is formed with come from the covariance through that block.
+     * A call FAILS when a pivot D[j] is not > 0, |d|^2 is not > 0 or a number on the way is not finite: R_acc is updated all the same, `failures`
+     * counts it and every beam keeps the weights it had before the call -- the caller's fixed weights until the first call that succeeds.
+     * gsh_adaptive_beam_set takes effect at the next call, at its first sample; setting the mode starts from R_acc = 0 and both counters 0;
+     * NULL clears it: the caller's fixed weights (kept meanwhile; gsh_beam_get_weights returns them throughout) are in force again.
+     * GSH_ERR_INVALID, before any device is touched, for a null handle, forgetting outside [0, 1], a negative loading, a number that is not
+     * finite, an all-zero constraint vector of a beam the handle forms.  Refusals of the pushes are as on a fixed-weight handle and leave R_acc,
+     * weights and counters as they were.  Consecutive adaptive calls on different streams are ordered by the handle (an event recorded at the
+     * end of a chain, waited for at the start of the next).  gsh_beam_covariance* is unchanged on an adaptive handle and does not touch R_acc
+     * (the chain has scratch memory of its own); gsh_beam_time_process times the whole chain on copies of the state. */
+    typedef struct gsh_beam_adapt
+    {
+        double forgetting;  /* lambda in [0, 1]: R_acc <- lambda R_acc + R_block (0: every block on its own) */
+        double loading_rel; /* >= 0 */
+        double loading_abs; /* >= 0; delta = loading_rel * (sum_i Re R_acc[i][i]) / A + loading_abs, added to the diagonal */
+        double constraint_iq[GSH_ARRAY_MAX_BEAMS][GSH_ARRAY_MAX_ANTENNAS][2]; /* per beam the constraint vector c (entries a < n_antennas) */
+    } gsh_beam_adapt;
+    struct gsh_beam_adapt_state
+    {
+        uint64_t blocks;   /* adaptive calls completed since the mode was set (failed ones included) */
+        uint64_t failures; /* those of them that failed */
+        double delta;      /* the loading of the last call */
+        double r_acc_iq[GSH_ARRAY_MAX_ANTENNAS * GSH_ARRAY_MAX_ANTENNAS * 2]; /* the first A x A complex128, row-major, as gsh_beam_covariance */
+        float w_iq[GSH_ARRAY_MAX_BEAMS * GSH_ARRAY_MAX_ANTENNAS * 2];         /* the weights in force: the first n_beams x A complex64, row-major */
+    };
+    /* (the gsh_beam_* prefix is the fixed-weight entry points' list; the two calls of the adaptive mode carry a prefix of their own) */
+    int gsh_adaptive_beam_set(gsh_beam_t* b, const gsh_beam_adapt* conf); /* NULL: back to the caller's fixed weights */
+    /* synchronous: waits for the adaptive calls queued so far.  GSH_ERR_STATE on a handle that is not adaptive. */
+    int gsh_adaptive_beam_state(gsh_beam_t* b, struct gsh_beam_adapt_state* out);
     /* Direct (nearest-neighbour) resampler, the arithmetic of direct_resampler_conditioner_cc (src/algorithms/resampler/gnuradio_blocks/
      * direct_resampler_conditioner_cc.cc:39-129; used by the signal conditioner and the acquisition decimator, gnss_flowgraph.cc:1165-1209):
      * 32-bit phase accumulator, a sample is copied on every wrap.  Stateless form: outputs are numbered from the start of the stream,
