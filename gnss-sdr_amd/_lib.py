@@ -146,7 +146,8 @@ class TrkEpoch(C.Structure):
 
 
 class PackedFormat(C.Structure):
-    """gsh_packed_format (32 bytes): packed 2-bit / 4-bit front-end samples (sample_stream.PackedFormat builds it from a signal source's properties)."""
+    """gsh_packed_format (32 bytes): packed 2-bit / 4-bit front-end samples (sample_stream.PackedFormat builds it from a signal source's properties).
+    `reserved` is 0 but for the LabSat 3 Wideband families, where it is a flags word: bit 0 = digital I/O was recorded."""
     _fields_ = [
         ("family", C.c_int32),
         ("sample_type", C.c_int32),

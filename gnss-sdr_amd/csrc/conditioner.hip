@@ -868,7 +868,7 @@ extern "C"
         unsigned long long bytes = 0, count = 0;
         int rc = check_push(h, device_items, n_in, &bytes, &count);
         if (rc != GSH_OK) return rc;
-        const size_t align = h->plan.kind == gsh::COND_PACKED ? 1 : h->plan.item_bytes;
+        const size_t align = h->plan.kind == gsh::COND_PACKED ? gsh::packed_alignment(h->plan.packed) : h->plan.item_bytes;
         GSH_REQUIRE(n_in == 0 || reinterpret_cast<uintptr_t>(device_items) % align == 0, "the block must be aligned to its item (%zu bytes)", align);
         report(h, count, first_out, n_out);
         if (n_in == 0) return GSH_OK;

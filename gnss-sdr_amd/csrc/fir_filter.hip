@@ -418,6 +418,8 @@ extern "C"
                 unsigned long long bytes = 0;  // a packed block is whole input items (n_in samples of the format's channel)
                 int rc = gsh::packed_size(f->packed, n_in, &bytes);
                 if (rc != GSH_OK) return rc;
+                GSH_REQUIRE(reinterpret_cast<uintptr_t>(device_in) % gsh::packed_alignment(f->packed) == 0, "the packed block must be aligned to its %zu-byte register",
+                    gsh::packed_alignment(f->packed));
             }
         GSH_HIP(hipSetDevice(f->device));
         hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : f->stream;

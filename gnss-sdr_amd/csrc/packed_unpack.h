@@ -19,10 +19,21 @@ struct PackedCode
     int channel;      // NTLab RF channel; GSS6450: the band of the single-channel calls
     int nch;          // RF channels that share the stream item by item (GSS6450: words dealt round-robin over total_channels bands); else 1
     int swap;         // GSS6450 `endian`: the four bytes of every word are reversed before unpacking
+    // the register families (packed_registers.h: LabSat 2 / 3, LabSat 3 Wideband, SPIR); rbytes 0 for every family above, whose spb they leave 0
+    int rbytes;       // bytes per little-endian register: 2 (LabSat 2 / 3 item), 4 (SPIR item), 8 (LabSat 3 Wideband)
+    int spr;          // samples of one RF channel per register
+    int spare;        // unused bits at the top of the register (LabSat 3 Wideband: 64 - spr frame_bits)
+    int frame_bits;   // bits from one sample of a channel to the next: SFT = 2 QUA nch (LabSat 3 Wideband)
+    int qua;          // bits per I and per Q code (LabSat 3 Wideband: 1 .. 3)
+    unsigned spr_magic;  // register_div_magic(spr)
 };
-__host__ __device__ inline bool packed_multiband(const PackedCode& c) { return c.family == GSH_PACKED_GSS6450_2BIT || c.family == GSH_PACKED_GSS6450_4BIT; }
+__host__ __device__ inline bool packed_multiband(const PackedCode& c)
+{
+    return c.family == GSH_PACKED_GSS6450_2BIT || c.family == GSH_PACKED_GSS6450_4BIT || (c.family >= GSH_PACKED_LS3W_1BIT && c.family <= GSH_PACKED_LS3W_3BIT);
+}
 
-// validate *fmt (GSH_ERR_INVALID with a message) and reduce it
+// validate *fmt (GSH_ERR_INVALID with a message) and reduce it; the register families are reduced by register_code (labsat_unpack.hip)
+int register_code(const gsh_packed_format* fmt, PackedCode* out);
 int packed_code(const gsh_packed_format* fmt, PackedCode* out);
 // bytes holding n samples; GSH_ERR_INVALID when n is not a whole number of input items
 int packed_size(const PackedCode& c, unsigned long long n, unsigned long long* bytes);
@@ -32,6 +43,11 @@ int unpack_packed(const void* d_src, const PackedCode& c, unsigned long long fir
 // caller has validated the list (1 .. 8 distinct bands below c.nch)
 int unpack_packed_multi(const void* d_src, const PackedCode& c, unsigned long long first, unsigned long long n, int conj, const int* channels, int n_sel,
     float2* const* d_dst, hipStream_t s);
+// both of the above for a register family (c.rbytes != 0): n_sel = 1 with the code's own channel is the single-destination unpack
+int unpack_registers(const void* d_src, const PackedCode& c, unsigned long long first, unsigned long long n, int conj, const int* channels, int n_sel,
+    float2* const* d_dst, hipStream_t s);
+// alignment that packed_sample needs of a device block's base: the register size of a register family (read as one aligned load), else 1 (byte loads)
+inline size_t packed_alignment(const PackedCode& c) { return c.rbytes ? static_cast<size_t>(c.rbytes) : 1; }
 
 // a signed 2-bit field stored the reference's way -- `signed x : 2` assigned (c >> k) & 3 -- wraps in two's complement: 0, 1, -2, -1
 // (blocks/unpack_2bit_samples.cc:22-28, unpack_byte_2bit_cpx_samples.cc:26-29,80-89, unpack_byte_2bit_samples.cc:21-24,54-64)
@@ -116,9 +132,14 @@ __host__ __device__ __forceinline__ float2 packed_decode(const PackedCode& c, un
         }
 }
 
+}  // namespace gsh
+#include "packed_registers.h"
+namespace gsh
+{
 // sample k of the code's RF channel in the packed buffer `src` (sample 0 = the first of src[0])
 __host__ __device__ __forceinline__ float2 packed_sample(const unsigned char* src, const PackedCode& c, unsigned long long k)
 {
+    if (c.rbytes) return register_sample(src, c, k);
     return packed_decode(c, src[packed_byte_index(c, k)], static_cast<int>(k % static_cast<unsigned>(c.spb)));
 }
 }  // namespace gsh

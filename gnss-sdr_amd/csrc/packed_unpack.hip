@@ -4,6 +4,8 @@
 // floats it expands to with 16-byte stores; the samples in front of the first whole dword and behind the last one (a ring split at its capacity
 // boundary starts inside a byte) go one by one through the same decoder, the way convert_kernel treats head, tail and odd alignment.
 // The multi-band GSS6450 families go through unpack_fanout_kernel: one pass over the block writes up to 8 bands, each to a destination of its own.
+// The register families (LabSat 2 / 3, LabSat 3 Wideband, SPIR: packed_registers.h) are validated and unpacked in labsat_unpack.hip; the entry points
+// at the end of this file serve both kinds.
 #include "packed_unpack.h"
 
 namespace gsh
@@ -183,6 +185,7 @@ int launch_fanout(const FanoutArgs& a, const PackedCode& c, hipStream_t s)
 int packed_code(const gsh_packed_format* f, PackedCode* out)
 {
     GSH_REQUIRE(f != nullptr && out != nullptr, "null packed format");
+    if (f->family >= GSH_PACKED_LABSAT_2BIT && f->family <= GSH_PACKED_SPIR_1BIT) return register_code(f, out);  // (labsat_unpack.hip)
     GSH_REQUIRE(f->reserved == 0, "gsh_packed_format.reserved must be 0");
     const bool gss = f->family == GSH_PACKED_GSS6450_2BIT || f->family == GSH_PACKED_GSS6450_4BIT;
     if (gss)
@@ -258,6 +261,14 @@ int packed_code(const gsh_packed_format* f, PackedCode* out)
 
 int packed_size(const PackedCode& c, unsigned long long n, unsigned long long* bytes)
 {
+    if (c.rbytes)
+        {
+            const unsigned long long spr = static_cast<unsigned long long>(c.spr);
+            GSH_REQUIRE(n % spr == 0, "%llu samples are not a whole number of %d-byte %s (%d samples per RF channel in each)", n, c.rbytes,
+                c.rbytes == 8 ? "registers" : "items", c.spr);
+            *bytes = n / spr * static_cast<unsigned long long>(c.rbytes);  // (the RF channels of LabSat 3 Wideband share every register)
+            return GSH_OK;
+        }
     const unsigned long long per_item = static_cast<unsigned long long>(c.spb) * c.item_bytes;
     GSH_REQUIRE(n % per_item == 0, "%llu samples are not a whole number of input items (%llu samples per %d-byte item)", n, per_item, c.item_bytes);
     *bytes = n / static_cast<unsigned long long>(c.spb) * static_cast<unsigned long long>(c.nch);  // (nch bands share the stream word by word)
@@ -268,6 +279,7 @@ int unpack_packed_multi(const void* d_src, const PackedCode& c, unsigned long lo
     float2* const* d_dst, hipStream_t s)
 {
     if (n == 0) return GSH_OK;
+    if (c.rbytes) return unpack_registers(d_src, c, first, n, conj, channels, n_sel, d_dst, s);
     GSH_REQUIRE(packed_multiband(c) && n_sel >= 1 && n_sel <= FAN_MAX && n_sel <= c.nch, "%d bands of packed family %d", n_sel, c.family);
     GSH_REQUIRE((reinterpret_cast<uintptr_t>(d_src) & 3u) == 0, "packed 32-bit words must be 4-byte aligned");
     FanoutArgs a{};
@@ -287,9 +299,9 @@ int unpack_packed_multi(const void* d_src, const PackedCode& c, unsigned long lo
 int unpack_packed(const void* d_src, const PackedCode& c, unsigned long long first, unsigned long long n, int conj, void* d_dst, hipStream_t s)
 {
     if (n == 0) return GSH_OK;
-    if (packed_multiband(c))
+    if (packed_multiband(c) || c.rbytes)
         {
-            // one band of a multi-band block: the fan-out kernel with a single destination
+            // one band of a multi-band block: the fan-out kernel with a single destination (a register family: its one kernel, labsat_unpack.hip)
             const int ch = c.channel;
             float2* dst = static_cast<float2*>(d_dst);
             return unpack_packed_multi(d_src, c, first, n, conj, &ch, 1, &dst, s);

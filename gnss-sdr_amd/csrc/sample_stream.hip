@@ -793,6 +793,8 @@ extern "C"
         int rc = gsh::packed_ring_format(fmt, n, &c, &nbytes);
         if (rc != GSH_OK) return rc;
         GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
+        GSH_REQUIRE(reinterpret_cast<uintptr_t>(device_bytes) % gsh::packed_alignment(c) == 0, "device_bytes: the registers of packed family %d must be %zu-byte aligned",
+            fmt->family, gsh::packed_alignment(c));
         if (first_index) *first_index = s->next;
         if (n == 0) return GSH_OK;
         GSH_HIP(hipSetDevice(s->device));
@@ -862,6 +864,8 @@ extern "C"
         int ch[8];
         int rc = packed_multi_args(rings, channels, n_rings, fmt, device_bytes, n, &c, &nbytes, ch);
         if (rc != GSH_OK) return rc;
+        GSH_REQUIRE(reinterpret_cast<uintptr_t>(device_bytes) % gsh::packed_alignment(c) == 0, "device_bytes: the registers of packed family %d must be %zu-byte aligned",
+            fmt->family, gsh::packed_alignment(c));
         if (first_index)
             for (int i = 0; i < n_rings; i++) first_index[i] = rings[i]->next;
         if (n == 0) return GSH_OK;

@@ -25,17 +25,24 @@ class PackedFormat:
     """gsh_packed_format: packed 2-bit / 4-bit front-end samples, unpacked on the device the way the reference's signal source unpacks them
     (include/gnss_sdr_hip.h).  Build it from the source's configuration with from_signal_source()."""
     TWO_BIT, TWO_BIT_CPX, FOUR_BIT_CPX, NSR, NTLAB, GSS6450_2BIT, GSS6450_4BIT = 1, 2, 3, 4, 5, 6, 7
+    # the register families: LabSat 2 / 3 (16-bit items), LabSat 3 Wideband (64-bit registers, QUA 1 .. 3) and SPIR (32-bit items).  Their layout is in
+    # the recording, not in the configuration: from_labsat_header(), from_ls3w_ini()
+    LABSAT_2BIT, LABSAT_4BIT, LS3W_1BIT, LS3W_2BIT, LS3W_3BIT, SPIR_1BIT = 8, 9, 10, 11, 12, 13
+    DIGITAL_IO = 1   # flags bit of the LS3W families: digital I/O was recorded beside the RF channels
+    LS3W_SAMPLES_PER_REGISTER = {(1, 1): (32, 30), (1, 2): (16, 15), (1, 3): (10, 10), (2, 1): (16, 15), (2, 2): (8, 7), (2, 3): (5, 5),
+                                 (3, 1): (10, 10), (3, 2): (5, 5), (3, 3): (3, 3)}   # (QUA, CHN): (without, with) digital I/O
     REAL, IQ, QI = 0, 1, 2
     IMPLEMENTATIONS = {"Two_Bit_Packed_File_Signal_Source": TWO_BIT, "Two_Bit_Cpx_File_Signal_Source": TWO_BIT_CPX,
                        "Four_Bit_Cpx_File_Signal_Source": FOUR_BIT_CPX, "Nsr_File_Signal_Source": NSR, "NTLab_File_Signal_Source": NTLAB,
-                       "Spir_GSS6450_File_Signal_Source": GSS6450_4BIT}   # (adc_bits picks GSS6450_2BIT / GSS6450_4BIT)
+                       "Spir_GSS6450_File_Signal_Source": GSS6450_4BIT,   # (adc_bits picks GSS6450_2BIT / GSS6450_4BIT)
+                       "Spir_File_Signal_Source": SPIR_1BIT}
     SAMPLE_TYPES = {"real": REAL, "iq": IQ, "qi": QI}
 
     def __init__(self, family: int, sample_type: int = REAL, item_size: int = 1, big_endian_bytes: bool = False, big_endian_items: bool = False,
-                 rf_channels: int = 0, channel: int = 0):
+                 rf_channels: int = 0, channel: int = 0, flags: int = 0):
         self.family, self.sample_type, self.item_size = int(family), int(sample_type), int(item_size)
         self.big_endian_bytes, self.big_endian_items = int(big_endian_bytes), int(big_endian_items)
-        self.rf_channels, self.channel = int(rf_channels), int(channel)
+        self.rf_channels, self.channel, self.flags = int(rf_channels), int(channel), int(flags)
 
     @classmethod
     def from_signal_source(cls, implementation: str, **properties) -> "PackedFormat":
@@ -44,7 +51,18 @@ class PackedFormat:
         four_bit_cpx_file_signal_source.cc:38: sample_type iq; ntlab_file_signal_source.cc:41-42: RF_channels 4).  `channel` (not a reference
         property) picks the RF channel of an NTLab stream for unpack_device / a packed FirFilter.  Spir_GSS6450_File_Signal_Source
         (spir_gss6450_file_signal_source.cc:46-55): adc_bits 4, total_channels 1, sel_ch 1, endian false; the single-channel calls take band
-        sel_ch - 1.  Other properties of the source are ignored."""
+        sel_ch - 1.  Spir_File_Signal_Source: the 1-bit SPIR family; its item_type falls back to int whatever it says (spir_file_signal_source.cc:50-58).
+        Labsat_Signal_Source: the layout is in the recording, so give the file's first 1 024 bytes as header= (LabSat 2 / 3) or the text of the .ini beside
+        a .ls3w file as ini= (LabSat 3 Wideband), with the reference's selected_channel and digital_io_enabled.  Other properties of the source are
+        ignored."""
+        if implementation == "Labsat_Signal_Source":
+            sel = int(properties.get("selected_channel", 1))
+            if properties.get("header") is not None:
+                return cls.from_labsat_header(properties["header"], sel)[0]
+            if properties.get("ini") is not None:
+                return cls.from_ls3w_ini(properties["ini"], sel, bool(_flag(properties.get("digital_io_enabled", False))))
+            raise ValueError("Labsat_Signal_Source: the layout is in the recording, not in the configuration: pass header= (the file's first 1 024 bytes) or "
+                             "ini= (the text of the .ini of a .ls3w file), or call PackedFormat.from_labsat_header() / from_ls3w_ini()")
         if implementation not in cls.IMPLEMENTATIONS:
             raise ValueError(f"{implementation!r} is not a packed signal source ({', '.join(cls.IMPLEMENTATIONS)})")
         fam = cls.IMPLEMENTATIONS[implementation]
@@ -54,6 +72,8 @@ class PackedFormat:
                 raise ValueError(f"adc_bits {adc_bits}: the reference unpacks 2 and 4 only (unpack_spir_gss6450_samples.cc:44-104)")
             return cls(cls.GSS6450_2BIT if adc_bits == 2 else cls.GSS6450_4BIT, cls.IQ, 4, False, _flag(properties.get("endian", False)),
                        rf_channels=int(properties.get("total_channels", 1)), channel=int(properties.get("sel_ch", 1)) - 1)
+        if fam == cls.SPIR_1BIT:
+            return cls(fam, cls.IQ, 4)
         item_type = properties.get("item_type", "byte")
         if item_type not in (("byte", "short") if fam == cls.TWO_BIT else ("byte",)):
             raise ValueError(f"item_type {item_type!r} is not supported by {implementation}")
@@ -70,32 +90,115 @@ class PackedFormat:
             return cls(fam, cls.REAL, rf_channels=int(properties.get("RF_channels", 4)), channel=int(properties.get("channel", 0)))
         return cls(fam, cls.IQ if fam == cls.TWO_BIT_CPX else cls.REAL)
 
+    @classmethod
+    def from_labsat_header(cls, header: bytes, selected_channel: int = 1) -> "tuple[PackedFormat, int]":
+        """(format, data offset) of a LabSat 2 / LabSat 3 file from its header, read the way the reference reads it (parse_header,
+        gnuradio_blocks/labsat23_source.cc:363-583): bytes 0-7 zero, 8-10 "LS2" / "LS3", 11 sub-version, 12-15 header length (little-endian: where the
+        samples start), 16-17 section id 2, 18-21 section length, 22 reference clock, 23 bits per sample (2 / 4), 24 channel selector (1..4; 0 = A + B is
+        refused as the reference refuses it, :496-500), 25-27 informational.  ValueError for anything the reference refuses."""
+        h = bytes(header)
+        if len(h) < 28:
+            raise ValueError(f"a LabSat header of {len(h)} bytes: at least 28 are read")
+        if any(h[:8]):
+            raise ValueError("no LabSat preamble: bytes 0-7 of the header are not zero")
+        if h[8:11] not in (b"LS2", b"LS3"):
+            raise ValueError(f"no LabSat version in the header: bytes 8-10 are {h[8:11]!r}, not LS2 / LS3")
+        data_offset = int.from_bytes(h[12:16], "little")
+        section_id = int.from_bytes(h[16:18], "little")
+        if section_id != 2:
+            raise ValueError(f"LabSat header: section id {section_id}, section 2 is not available")
+        bits, selector = h[23], h[24]
+        if bits not in (2, 4):
+            raise ValueError(f"LabSat header: unknown bits per sample {bits} (2 or 4)")
+        if selector > 4:
+            raise ValueError(f"LabSat header: unknown channel selector {selector}")
+        if int(selected_channel) == 2 and selector != 0:
+            raise ValueError("selected_channel 2, but the file has only one channel")
+        if selector == 0:
+            raise ValueError("the file holds channels A + B: more than one channel is not supported for LabSat 2 / 3 files")
+        if int(selected_channel) != 1:
+            raise ValueError(f"selected_channel {selected_channel}: a LabSat 2 / 3 file carries one RF channel")
+        return cls(cls.LABSAT_2BIT if bits == 2 else cls.LABSAT_4BIT, cls.IQ, 2), data_offset
+
+    @classmethod
+    def from_ls3w_ini(cls, text: str, selected_channel: int = 1, digital_io_enabled: bool = False) -> "PackedFormat":
+        """The format of a LabSat 3 Wideband (.ls3w) recording from the text of the .ini file beside it, read the way the reference reads it (read_ls3w_ini,
+        gnuradio_blocks/labsat23_source.cc:678-787): [config] QUA (else QUAN_A), CHN and SFT; QUA above 3 or CHN above 3 is refused; an SFT other than
+        2 QUA CHN is replaced by it (:780-784).  The single-channel calls take RF channel selected_channel - 1."""
+        import configparser
+        ini = configparser.ConfigParser(strict=False, interpolation=None)
+        ini.optionxform = str
+        ini.read_string(text)
+        if not ini.has_section("config"):
+            raise ValueError("the .ini of a LabSat 3 Wideband recording has no [config] section")
+        cfg = ini["config"]
+        qua = cfg.get("QUA") or cfg.get("QUAN_A")
+        if not qua:
+            raise ValueError("[config] has neither QUA nor QUAN_A")
+        qua, chn = int(qua), int(cfg.get("CHN") or 0)
+        if not 1 <= qua <= 3:
+            raise ValueError(f"QUA {qua}: a sample quantization of 1, 2 or 3 bits is supported")
+        if not 1 <= chn <= 3:
+            raise ValueError(f"CHN {chn}: recordings of 1, 2 or 3 RF channels are supported")
+        sft = 2 * qua * chn   # (a different SFT in the file is not valid: replaced, as the reference replaces it)
+        sel = int(selected_channel)
+        if not 1 <= sel <= chn:
+            raise ValueError(f"selected_channel {sel}: the recording has {chn} RF channel(s)")
+        f = cls(cls.LS3W_1BIT + qua - 1, cls.IQ, 8, rf_channels=chn, channel=sel - 1, flags=cls.DIGITAL_IO if digital_io_enabled else 0)
+        assert f.samples_per_item * sft <= 64
+        return f
+
     def with_channel(self, channel: int) -> "PackedFormat":
-        return PackedFormat(self.family, self.sample_type, self.item_size, self.big_endian_bytes, self.big_endian_items, self.rf_channels, channel)
+        return PackedFormat(self.family, self.sample_type, self.item_size, self.big_endian_bytes, self.big_endian_items, self.rf_channels, channel,
+                            self.flags)
+
+    @property
+    def is_register_family(self) -> bool:
+        return self.LABSAT_2BIT <= self.family <= self.SPIR_1BIT
 
     @property
     def is_complex(self) -> bool:
-        return self.family in (self.TWO_BIT_CPX, self.FOUR_BIT_CPX, self.GSS6450_2BIT, self.GSS6450_4BIT) or (self.family == self.TWO_BIT and self.sample_type != self.REAL)
+        return (self.family in (self.TWO_BIT_CPX, self.FOUR_BIT_CPX, self.GSS6450_2BIT, self.GSS6450_4BIT) or self.is_register_family
+                or (self.family == self.TWO_BIT and self.sample_type != self.REAL))
 
     @property
     def samples_per_byte(self) -> int:
-        """samples of one RF channel per packed byte (GSS6450: per byte of the channel's own words)"""
+        """samples of one RF channel per packed byte (GSS6450: per byte of the channel's own words).  Not meaningful for the register families, whose
+        fields straddle bytes: samples_per_item / item_bytes"""
+        if self.is_register_family:
+            raise ValueError(f"packed family {self.family} has no whole number of samples per byte: use samples_per_item / item_bytes")
         if self.family == self.TWO_BIT:
             return 2 if self.is_complex else 4
         return {self.TWO_BIT_CPX: 2, self.FOUR_BIT_CPX: 1, self.NSR: 4, self.NTLAB: 1, self.GSS6450_2BIT: 2, self.GSS6450_4BIT: 1}[self.family]
 
     @property
+    def item_bytes(self) -> int:
+        """bytes of one input item: the 64-bit register of LS3W, the 16-bit item of LabSat 2 / 3, the 32-bit item of SPIR and word of GSS6450, the byte or
+        short of the other families"""
+        return self.item_size
+
+    @property
+    def samples_per_item(self) -> int:
+        """samples of one RF channel in one input item (LS3W: in one register, which holds as many of every RF channel)"""
+        if self.LS3W_1BIT <= self.family <= self.LS3W_3BIT:
+            return self.LS3W_SAMPLES_PER_REGISTER[(self.family - self.LS3W_1BIT + 1, self.rf_channels)][self.flags & self.DIGITAL_IO]
+        if self.is_register_family:
+            return {self.LABSAT_2BIT: 8, self.LABSAT_4BIT: 4, self.SPIR_1BIT: 1}[self.family]
+        return self.samples_per_byte * self.item_size
+
+    @property
     def interleaved_channels(self) -> int:
-        """RF channels whose words share the packed stream (GSS6450 total_channels); 1 for every other family"""
+        """RF channels whose words share the packed stream (GSS6450 total_channels); 1 for every other family (the RF channels of LS3W share every
+        register, not the stream item by item)"""
         return max(1, self.rf_channels) if self.family in (self.GSS6450_2BIT, self.GSS6450_4BIT) else 1
 
     def struct(self) -> "_lib.PackedFormat":
         return _lib.PackedFormat(self.family, self.sample_type, self.item_size, self.big_endian_bytes, self.big_endian_items, self.rf_channels,
-                                 self.channel, 0)
+                                 self.channel, self.flags)
 
     def __repr__(self):
         return (f"PackedFormat(family={self.family}, sample_type={self.sample_type}, item_size={self.item_size}, big_endian_bytes={self.big_endian_bytes}, "
-                f"big_endian_items={self.big_endian_items}, rf_channels={self.rf_channels}, channel={self.channel})")
+                f"big_endian_items={self.big_endian_items}, rf_channels={self.rf_channels}, channel={self.channel}, flags={self.flags})")
 
 
 def packed_bytes(fmt: PackedFormat, n_samples: int) -> int:
@@ -117,7 +220,11 @@ def unpack_device(device: int, fmt: PackedFormat, src_ptr: int, first_sample: in
 
 def _packed_host(fmt: PackedFormat, data, n_samples):
     a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data).view(np.uint8).reshape(-1)
-    n = a.size * fmt.samples_per_byte // fmt.interleaved_channels if n_samples is None else int(n_samples)
+    if n_samples is not None:
+        return a, int(n_samples)
+    if fmt.is_register_family:
+        return a, a.size // fmt.item_bytes * fmt.samples_per_item
+    n = a.size * fmt.samples_per_byte // fmt.interleaved_channels
     return a, n
 
 

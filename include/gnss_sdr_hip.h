@@ -395,6 +395,30 @@ extern "C"
      *                            nibble / byte, I in the low half of the field and Q in the high half, two's complement, no 2s + 1.  Complex; a
      *                            packed buffer starts at a frame boundary (band 0's word).  GNU Radio's deinterleave and endian_swap are restated
      *                            from their documented behaviour.
+     *   GSH_PACKED_LABSAT_2BIT   Labsat_Signal_Source, LabSat 2 / LabSat 3 files with one RF channel (blocks/labsat23_source.cc:363-583 parse_header,
+     *   GSH_PACKED_LABSAT_4BIT   :586-658 decode_samples_one_channel): 16-bit little-endian items.  2 bits per sample: 8 complex samples per item, sample i
+     *                            has I = bit 15 - 2i, Q = bit 14 - 2i, value 2 b - 1.  4 bits: 4 samples per item, I sign = bit 15 - 4i, Q sign = bit
+     *                            14 - 4i, I magnitude = bit 13 - 4i, Q magnitude = bit 12 - 4i; (sign, magnitude) 00 -> +1, 01 -> +2, 11 -> -1, 10 -> -2.
+     *   GSH_PACKED_LS3W_1BIT     Labsat_Signal_Source, LabSat 3 Wideband (.ls3w) with QUA = 1 / 2 / 3 bits each for I and Q and rf_channels = CHN (1..3)
+     *   GSH_PACKED_LS3W_2BIT     RF channels: a run of 64-bit little-endian registers of spr samples of EVERY channel (blocks/labsat23_source.cc:954-1034
+     *   GSH_PACKED_LS3W_3BIT     number_of_samples_per_ls3w_register; without / with digital I/O recorded):
+     *                                QUA 1: CHN 1 32 / 30, CHN 2 16 / 15, CHN 3 10 / 10
+     *                                QUA 2: CHN 1 16 / 15, CHN 2  8 /  7, CHN 3  5 /  5
+     *                                QUA 3: CHN 1 10 / 10, CHN 2  5 /  5, CHN 3  3 /  3
+     *                            With SFT = 2 QUA CHN, spare = 64 - spr SFT bits (0, 4, 8 or 10) at the TOP of the register are not samples.  Sample i
+     *                            of channel c starts o = spare + i SFT + 2 QUA c bits below the top (:944-948,1037-1053): the I code is bits 63 - o ..
+     *                            63 - o - QUA + 1, most significant first, the Q code the next QUA bits.  Value (generate_mapping, :43-62), half =
+     *                            2^(QUA-1): code < half -> (code + 1) / half, else (code - 2^QUA) / half; every value is a multiple of 0.25.
+     *                            DEVIATION: the reference as compiled cannot be used as the yardstick here.  Its extract_bits (:67-74) indexes
+     *                            bs[64 - start - i + 1], bit 65 - start - i: outside the 64-bit std::bitset for offsets 0 and 1 (undefined behaviour)
+     *                            and elsewhere two bits above the position that the surrounding code implies (:1039 "Earlier samples are written in the
+     *                            MSBs", the spare bits counted from the top, the LabSat 4 path taking "48 MSBs" with offsets 0 and 24).  This library
+     *                            reads bit 63 - start - i.  Not covered: LabSat 4, two-channel LabSat 2 / 3 files (refused by the reference, :496-500),
+     *                            and the host's file handling (the _0000.LS3 sequence, seconds_to_skip, throttling).
+     *   GSH_PACKED_SPIR_1BIT     Spir_File_Signal_Source (adapters/spir_file_signal_source.cc:50-58): blocks/unpack_intspir_1bit_samples.cc:36-68 with one
+     *                            channel: one complex sample per 32-bit little-endian int, I = bit 0, Q = bit 1, +32767 when set and -32767 when clear.
+     * The six families above are complex (sample_type IQ), take big_endian_bytes = big_endian_items = 0, and their blocks are whole items / registers
+     * whose base is aligned to the item (2, 8 and 4 bytes).  The LS3W families are multi-band, as GSS6450.
      * The real families (TWO_BIT with sample_type real, NSR, NTLAB) are IF samples: they enter a ring through a packed FIR (gsh_fir_create_packed)
      * and gsh_stream_push_device, never directly.  Sample counts are samples of ONE RF channel and must be whole input items (the reference blocks
      * are sync_interpolators: they consume whole items).  Zero-initialise the descriptor and set what applies. */
@@ -405,25 +429,31 @@ extern "C"
 #define GSH_PACKED_NTLAB 5
 #define GSH_PACKED_GSS6450_2BIT 6
 #define GSH_PACKED_GSS6450_4BIT 7
+#define GSH_PACKED_LABSAT_2BIT 8
+#define GSH_PACKED_LABSAT_4BIT 9
+#define GSH_PACKED_LS3W_1BIT 10
+#define GSH_PACKED_LS3W_2BIT 11
+#define GSH_PACKED_LS3W_3BIT 12
+#define GSH_PACKED_SPIR_1BIT 13
 #define GSH_PACKED_REAL 0 /* sample_type "real" */
 #define GSH_PACKED_IQ 1   /* sample_type "iq" */
 #define GSH_PACKED_QI 2   /* sample_type "qi" */
     typedef struct
     {
-        int32_t family;           /* GSH_PACKED_TWO_BIT .. GSH_PACKED_GSS6450_4BIT (the SignalSource.implementation) */
+        int32_t family;           /* GSH_PACKED_TWO_BIT .. GSH_PACKED_SPIR_1BIT (the SignalSource.implementation) */
         int32_t sample_type;      /* TWO_BIT: "sample_type", default real (two_bit_packed_file_signal_source.cc:39); FOUR_BIT_CPX: iq / qi, default iq
                                    * (four_bit_cpx_file_signal_source.cc:38); REAL for NSR and NTLAB; IQ for TWO_BIT_CPX */
-        int32_t item_size;        /* TWO_BIT: 1 ("item_type" byte, the default of FileSourceBase) or 2 (short); GSS6450: 4 (the 32-bit word); every other
-                                   * family: 1 */
+        int32_t item_size;        /* TWO_BIT: 1 ("item_type" byte, the default of FileSourceBase) or 2 (short); GSS6450: 4 (the 32-bit word); LABSAT: 2;
+                                   * LS3W: 8 (the register); SPIR: 4; every other family: 1 */
         int32_t big_endian_bytes; /* TWO_BIT: "big_endian_bytes", default false (two_bit_packed_file_signal_source.cc:41): sample order within a byte reversed */
         int32_t big_endian_items; /* TWO_BIT: "big_endian_items", default true (:40): with item_size 2 the two bytes of an item swap first; little-endian
                                    * short items are read as bytes (:63-77).  GSS6450: "endian", default false (spir_gss6450_file_signal_source.cc:51): the
                                    * four bytes of every word are reversed before unpacking */
         int32_t rf_channels;      /* NTLAB: "RF_channels", default 4 (ntlab_file_signal_source.cc:41-42), 4 only; GSS6450: "total_channels", 1..8 (0 reads as
-                                   * 1); every other family: 0 or 1 */
+                                   * 1); LS3W: CHN, 1..3; every other family: 0 or 1 */
         int32_t channel;          /* NTLAB: the RF channel unpacked by gsh_unpack_device / the packed FIR (0..3); GSS6450: the band the single-channel calls
-                                   * take, "sel_ch" - 1; every other family: 0 */
-        int32_t reserved;         /* 0 */
+                                   * take, "sel_ch" - 1; LS3W: "selected_channel" - 1 (0..2); every other family: 0 */
+        int32_t reserved;         /* 0; LS3W: a flags word, bit 0 = digital I/O was recorded ("digital_io_enabled"), every other bit 0 */
     } gsh_packed_format;
     /* packed bytes that hold n_samples samples per RF channel; GSH_ERR_INVALID for a bad descriptor or a count that is not whole items.  No GPU. */
     int gsh_packed_bytes(const gsh_packed_format* fmt, uint64_t n_samples, uint64_t* bytes);
@@ -432,12 +462,13 @@ extern "C"
     int gsh_packed_decode_host(const gsh_packed_format* fmt, const void* bytes, uint64_t first_sample, uint64_t n_samples, float* out_iq);
     /* samples [first_sample, first_sample + n_samples) of the packed buffer d_src (sample 0 = the first of its first byte) -> d_dst: complex64 for
      * the complex families (conjugated when inverted_spectrum), float32 of fmt->channel for the real ones (inverted_spectrum must be 0).
-     * first_sample may fall inside a byte; d_dst 8-byte aligned (complex) or 4-byte aligned (real).  Asynchronous on hip_stream. */
+     * first_sample may fall inside a byte or a register, and n_samples need not end at one; d_src aligned to the item of a LABSAT / LS3W / SPIR family;
+     * d_dst 8-byte aligned (complex) or 4-byte aligned (real).  Asynchronous on hip_stream. */
     int gsh_unpack_device(int device, const gsh_packed_format* fmt, const void* d_src, uint64_t first_sample, uint64_t n_samples, int inverted_spectrum,
         void* d_dst, void* hip_stream);
-    /* the same for several bands of a multi-band family (GSS6450) in ONE pass over the packed block: samples [first_sample, first_sample + n_samples)
+    /* the same for several bands of a multi-band family (GSS6450, LS3W) in ONE pass over the packed block: samples [first_sample, first_sample + n_samples)
      * of band channels[i] -> complex64 at d_dst[i] (8-byte aligned), i < n_channels <= rf_channels.  fmt->channel is not consulted.  GSH_ERR_INVALID
-     * for a family without several bands, a band out of range or named twice, a null or misaligned destination.  d_src is 4-byte aligned.
+     * for a family without several bands, a band out of range or named twice, a null or misaligned destination.  d_src is 4-byte aligned (GSS6450) or 8-byte aligned (LS3W).
      * Asynchronous on hip_stream. */
     int gsh_unpack_device_multi(int device, const gsh_packed_format* fmt, const void* d_src, uint64_t first_sample, uint64_t n_samples,
         int inverted_spectrum, const int32_t* channels, int n_channels, void* const* d_dst, void* hip_stream);
@@ -449,7 +480,7 @@ extern "C"
         void* hip_stream, uint64_t* first_index);
     int gsh_stream_push_packed_pinned_async(gsh_stream_t* s, const gsh_packed_format* fmt, const void* bytes, uint64_t n_samples, int inverted_spectrum,
         uint64_t* first_index);
-    /* One push of a multi-band packed block (GSS6450) into n_rings rings: band channels[i] goes to rings[i].  The block crosses PCIe once and
+    /* One push of a multi-band packed block (GSS6450, LS3W) into n_rings rings: band channels[i] goes to rings[i].  The block crosses PCIe once and
      * one pass over it writes every ring; afterwards each ring is, bit for bit and index for index, what the single-ring call of the same name
      * with fmt->channel = channels[i] would have left (resident range, mirror, push event, live words), and gsh_stream_wait / _wait_copied /
      * _wait_copied_upto work on every ring of the call.  Rings may differ in capacity, window and next index; they lie on one device.  n_samples
