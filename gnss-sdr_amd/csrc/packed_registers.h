@@ -4,6 +4,7 @@
 // the host decode, the unpack kernels (labsat_unpack.hip), the packed FIR and the conditioner all reach it, the last three through packed_sample.
 // The 16-bit items of LabSat 2 / 3 and the 32-bit items of SPIR go through it as registers of 16 and 32 bits (spare 0), not through the byte decoder.
 // Reference (src/algorithms/signal_source/gnuradio_blocks/, "blocks/" below): labsat23_source.cc, unpack_intspir_1bit_samples.cc.
+// LabSat 4 is the one family here that is NOT a run of equal registers: see "LabSat 4" below.
 //
 // DEVIATION from the reference as compiled, LabSat 3 Wideband only: extract_bits (blocks/labsat23_source.cc:67-74) indexes bs[64 - start - i + 1], bit
 // 65 - start - i of the 64-bit std::bitset: outside the bitset for offsets 0 and 1 (undefined behaviour) and elsewhere two bits above the position the
@@ -94,9 +95,38 @@ __host__ __device__ __forceinline__ unsigned long long register_load(const unsig
 #endif
 }
 
+// LabSat 4 (blocks/labsat23_source.cc:92-121 write_samples_ls4, :1262-1301 read_ls4_data / parse_ls4_data).  A block is a run of ROUNDS; a round holds one
+// buffer of regs[s] 64-bit little-endian registers per recorded channel slot s, in the order A, B, C, and the buffers may differ in size.  Inside one
+// buffer the registers form ONE bit stream, register 0 first and each register from its top bit down: sample j of the round starts at bit 2 QUA j, the
+// I code is its first QUA bits (most significant first) and the Q code the next QUA.  For QUA 1, 2, 4, 8 a field never leaves its register; at QUA 12
+// three registers hold 8 samples and samples 2 and 5 of such a triple straddle two registers (regs is a multiple of 3, so never the buffer's end).
+// ls4_field: the 2 QUA bits that start `o` bits below the top of `lo` and run on into the top of `hi` (read only when o + bits > 64).
+__host__ __device__ __forceinline__ unsigned ls4_field(unsigned long long lo, unsigned long long hi, unsigned o, unsigned bits)
+{
+    const unsigned end = o + bits;
+    const unsigned long long v = end <= 64u ? lo >> (64u - end) : (lo << (end - 64u)) | (hi >> (128u - end));
+    return static_cast<unsigned>(v) & ((1u << bits) - 1u);
+}
+// generate_mapping (:43-62) on both codes of a field: code < half -> (code + 1) / half, else (code - 2^QUA) / half; scale = 1 / half is a power of two
+__host__ __device__ __forceinline__ float2 ls4_value(unsigned f, int qua, float scale)
+{
+    const int mask = (1 << qua) - 1, half = 1 << (qua - 1);
+    const int ci = static_cast<int>(f >> qua) & mask, cq = static_cast<int>(f) & mask;
+    return make_float2(static_cast<float>(ci < half ? ci + 1 : ci - 2 * half) * scale, static_cast<float>(cq < half ? cq + 1 : cq - 2 * half) * scale);
+}
+
 // sample k of the code's RF channel: the register families' half of packed_sample
 __host__ __device__ __forceinline__ float2 register_sample(const unsigned char* src, const PackedCode& c, unsigned long long k)
 {
+    if (c.ls4)
+        {
+            const unsigned long long round = k / c.ls4_s;
+            const unsigned b = static_cast<unsigned>(k - round * c.ls4_s) * static_cast<unsigned>(c.frame_bits), o = b & 63u;
+            const unsigned long long r = round * c.ls4_round + c.ls4_base + (b >> 6);
+            const unsigned long long lo = register_load(src, c, r);
+            const unsigned long long hi = o + static_cast<unsigned>(c.frame_bits) > 64u ? register_load(src, c, r + 1ull) : 0ull;
+            return ls4_value(ls4_field(lo, hi, o, static_cast<unsigned>(c.frame_bits)), c.qua, c.ls4_scale);
+        }
     const unsigned long long r = k / static_cast<unsigned>(c.spr);
     return register_decode(c, register_load(src, c, r), static_cast<int>(k - r * static_cast<unsigned>(c.spr)), c.channel);
 }

@@ -26,10 +26,20 @@ struct PackedCode
     int frame_bits;   // bits from one sample of a channel to the next: SFT = 2 QUA nch (LabSat 3 Wideband)
     int qua;          // bits per I and per Q code (LabSat 3 Wideband: 1 .. 3)
     unsigned spr_magic;  // register_div_magic(spr)
+    // LabSat 4 (ls4 = 1, rbytes 8): a block is a run of ROUNDS, each one buffer of registers per recorded channel slot.  spr: samples per register, or per
+    // triple of registers at QUA 12 (8); frame_bits = 2 QUA; nch = the slots described.  The arrays are read on the host only (the launcher, the checks).
+    int ls4;
+    unsigned ls4_s;        // samples of the selected slot per round: its registers x 32 / QUA
+    unsigned ls4_round;    // registers per round, every recorded slot together
+    unsigned ls4_base;     // register of the round at which the selected slot's buffer starts (ls4_off[channel])
+    float ls4_scale;       // 1 / half, half = 2^(QUA - 1)
+    unsigned ls4_off[3], ls4_regs[3];
 };
+__host__ __device__ inline bool packed_ls4(int family) { return family >= GSH_PACKED_LS4_1BIT && family <= GSH_PACKED_LS4_12BIT; }
 __host__ __device__ inline bool packed_multiband(const PackedCode& c)
 {
-    return c.family == GSH_PACKED_GSS6450_2BIT || c.family == GSH_PACKED_GSS6450_4BIT || (c.family >= GSH_PACKED_LS3W_1BIT && c.family <= GSH_PACKED_LS3W_3BIT);
+    return c.family == GSH_PACKED_GSS6450_2BIT || c.family == GSH_PACKED_GSS6450_4BIT || (c.family >= GSH_PACKED_LS3W_1BIT && c.family <= GSH_PACKED_LS3W_3BIT) ||
+           packed_ls4(c.family);
 }
 
 // validate *fmt (GSH_ERR_INVALID with a message) and reduce it; the register families are reduced by register_code (labsat_unpack.hip)
@@ -46,6 +56,8 @@ int unpack_packed_multi(const void* d_src, const PackedCode& c, unsigned long lo
 // both of the above for a register family (c.rbytes != 0): n_sel = 1 with the code's own channel is the single-destination unpack
 int unpack_registers(const void* d_src, const PackedCode& c, unsigned long long first, unsigned long long n, int conj, const int* channels, int n_sel,
     float2* const* d_dst, hipStream_t s);
+// LabSat 4: the slots of one multi call (each below c.nch) are recorded and hold the same number of registers per round; GSH_OK for every other family
+int ls4_check_channels(const PackedCode& c, const int* channels, int n_sel);
 // alignment that packed_sample needs of a device block's base: the register size of a register family (read as one aligned load), else 1 (byte loads)
 inline size_t packed_alignment(const PackedCode& c) { return c.rbytes ? static_cast<size_t>(c.rbytes) : 1; }
 

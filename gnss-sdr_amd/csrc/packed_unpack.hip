@@ -185,7 +185,7 @@ int launch_fanout(const FanoutArgs& a, const PackedCode& c, hipStream_t s)
 int packed_code(const gsh_packed_format* f, PackedCode* out)
 {
     GSH_REQUIRE(f != nullptr && out != nullptr, "null packed format");
-    if (f->family >= GSH_PACKED_LABSAT_2BIT && f->family <= GSH_PACKED_SPIR_1BIT) return register_code(f, out);  // (labsat_unpack.hip)
+    if ((f->family >= GSH_PACKED_LABSAT_2BIT && f->family <= GSH_PACKED_SPIR_1BIT) || packed_ls4(f->family)) return register_code(f, out);  // (labsat_unpack.hip)
     GSH_REQUIRE(f->reserved == 0, "gsh_packed_format.reserved must be 0");
     const bool gss = f->family == GSH_PACKED_GSS6450_2BIT || f->family == GSH_PACKED_GSS6450_4BIT;
     if (gss)
@@ -261,6 +261,15 @@ int packed_code(const gsh_packed_format* f, PackedCode* out)
 
 int packed_size(const PackedCode& c, unsigned long long n, unsigned long long* bytes)
 {
+    if (c.ls4)
+        {
+            // whole registers (whole triples at QUA 12) of the selected slot; a count that ends inside a round takes the whole round's bytes
+            const unsigned long long unit = static_cast<unsigned long long>(c.spr), S = c.ls4_s;
+            GSH_REQUIRE(n % unit == 0, "%llu samples are not a whole number of %s (%d samples of a channel in each)", n,
+                c.qua == 12 ? "24-byte triples of registers" : "8-byte registers", c.spr);
+            *bytes = (n + S - 1ull) / S * c.ls4_round * 8ull;
+            return GSH_OK;
+        }
     if (c.rbytes)
         {
             const unsigned long long spr = static_cast<unsigned long long>(c.spr);
@@ -366,7 +375,11 @@ extern "C"
         const int32_t* channels, int n_channels, void* const* d_dst, void* hip_stream)
     {
         gsh::PackedCode c;
-        int rc = gsh::packed_code(fmt, &c);
+        GSH_REQUIRE(fmt != nullptr, "null packed format");
+        gsh_packed_format f = *fmt;
+        // (LabSat 4: fmt->channel is not consulted either, but the reduced format carries the round geometry of a selected slot: the first one named)
+        if (gsh::packed_ls4(f.family) && channels != nullptr && n_channels >= 1) f.channel = channels[0];
+        int rc = gsh::packed_code(&f, &c);
         if (rc != GSH_OK) return rc;
         GSH_REQUIRE(gsh::packed_multiband(c), "packed family %d carries one band: gsh_unpack_device_multi takes the multi-band families (GSS6450)", fmt->family);
         GSH_REQUIRE(channels != nullptr && d_dst != nullptr, "null argument");
@@ -382,6 +395,8 @@ extern "C"
                 ch[i] = channels[i];
                 dst[i] = static_cast<float2*>(d_dst[i]);
             }
+        rc = gsh::ls4_check_channels(c, ch, n_channels);
+        if (rc != GSH_OK) return rc;
         GSH_REQUIRE(n_samples == 0 || d_src != nullptr, "null argument");
         rc = gsh::use_device(device);
         if (rc != GSH_OK) return rc;

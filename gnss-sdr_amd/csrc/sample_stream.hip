@@ -409,7 +409,7 @@ int packed_multi_args(gsh_stream_t* const* rings, const int32_t* channels, int n
 {
     GSH_REQUIRE(rings != nullptr && channels != nullptr && fmt != nullptr, "null argument");
     gsh_packed_format f = *fmt;
-    f.channel = 0;
+    f.channel = gsh::packed_ls4(f.family) && n_rings >= 1 ? channels[0] : 0;  // (LabSat 4: the round geometry is that of a selected slot)
     int rc = gsh::packed_ring_format(&f, n, c, nbytes);
     if (rc != GSH_OK) return rc;
     GSH_REQUIRE(gsh::packed_multiband(*c), "packed family %d carries one band: a multi-ring push takes the multi-band families (GSS6450)", fmt->family);
@@ -423,6 +423,8 @@ int packed_multi_args(gsh_stream_t* const* rings, const int32_t* channels, int n
             for (int j = 0; j < i; j++) GSH_REQUIRE(channels[j] != channels[i], "band %d is named twice", channels[i]);
             ch[i] = channels[i];
         }
+    rc = gsh::ls4_check_channels(*c, ch, n_rings);
+    if (rc != GSH_OK) return rc;
     return gsh::stream_multi_check_live(rings, n_rings, n);
 }
 }  // namespace

@@ -28,6 +28,9 @@ class PackedFormat:
     # the register families: LabSat 2 / 3 (16-bit items), LabSat 3 Wideband (64-bit registers, QUA 1 .. 3) and SPIR (32-bit items).  Their layout is in
     # the recording, not in the configuration: from_labsat_header(), from_ls3w_ini()
     LABSAT_2BIT, LABSAT_4BIT, LS3W_1BIT, LS3W_2BIT, LS3W_3BIT, SPIR_1BIT = 8, 9, 10, 11, 12, 13
+    # LabSat 4 (64-bit registers in rounds of one buffer per channel slot, QUA 1 / 2 / 4 / 8 / 12): ls4(), from_ls4_ini()
+    LS4_1BIT, LS4_2BIT, LS4_4BIT, LS4_8BIT, LS4_12BIT = 14, 15, 16, 17, 18
+    LS4_QUA = {1: LS4_1BIT, 2: LS4_2BIT, 4: LS4_4BIT, 8: LS4_8BIT, 12: LS4_12BIT}
     DIGITAL_IO = 1   # flags bit of the LS3W families: digital I/O was recorded beside the RF channels
     LS3W_SAMPLES_PER_REGISTER = {(1, 1): (32, 30), (1, 2): (16, 15), (1, 3): (10, 10), (2, 1): (16, 15), (2, 2): (8, 7), (2, 3): (5, 5),
                                  (3, 1): (10, 10), (3, 2): (5, 5), (3, 3): (3, 3)}   # (QUA, CHN): (without, with) digital I/O
@@ -53,12 +56,15 @@ class PackedFormat:
         (spir_gss6450_file_signal_source.cc:46-55): adc_bits 4, total_channels 1, sel_ch 1, endian false; the single-channel calls take band
         sel_ch - 1.  Spir_File_Signal_Source: the 1-bit SPIR family; its item_type falls back to int whatever it says (spir_file_signal_source.cc:50-58).
         Labsat_Signal_Source: the layout is in the recording, so give the file's first 1 024 bytes as header= (LabSat 2 / 3) or the text of the .ini beside
-        a .ls3w file as ini= (LabSat 3 Wideband), with the reference's selected_channel and digital_io_enabled.  Other properties of the source are
-        ignored."""
+        a .ls3w file as ini= (LabSat 3 Wideband), with the reference's selected_channel and digital_io_enabled; a filename= that ends in .ls4 makes ini=
+        the .ini of a LabSat 4 recording (the reference tells the generations apart by the extension, labsat23_source.cc:333-361).  Other properties of
+        the source are ignored."""
         if implementation == "Labsat_Signal_Source":
             sel = int(properties.get("selected_channel", 1))
             if properties.get("header") is not None:
                 return cls.from_labsat_header(properties["header"], sel)[0]
+            if properties.get("ini") is not None and str(properties.get("filename", "")).endswith((".ls4", ".LS4")):   # (generate_filename, :351-354)
+                return cls.from_ls4_ini(properties["ini"], sel)
             if properties.get("ini") is not None:
                 return cls.from_ls3w_ini(properties["ini"], sel, bool(_flag(properties.get("digital_io_enabled", False))))
             raise ValueError("Labsat_Signal_Source: the layout is in the recording, not in the configuration: pass header= (the file's first 1 024 bytes) or "
@@ -148,13 +154,92 @@ class PackedFormat:
         assert f.samples_per_item * sft <= 64
         return f
 
+    @classmethod
+    def ls4(cls, qua: int, regs, channel: int = 0) -> "PackedFormat":
+        """The LabSat 4 layout (QUA, regs): regs[s] 64-bit registers of channel slot s (A, B, C) per round, 0 for a slot that is not recorded; `channel`
+        is the selected slot (0-based).  The register counts travel in big_endian_bytes, big_endian_items and flags (gsh_packed_format)."""
+        if int(qua) not in cls.LS4_QUA:
+            raise ValueError(f"QUA {qua}: a LabSat 4 sample quantization of 1, 2, 4, 8 or 12 bits is supported")
+        regs = [int(r) for r in regs]
+        if not 1 <= len(regs) <= 3:
+            raise ValueError(f"{len(regs)} channel slots: a LabSat 4 layout describes 1 to 3 (A, B, C)")
+        r = regs + [0] * (3 - len(regs))
+        return cls(cls.LS4_QUA[int(qua)], cls.IQ, 8, r[0], r[1], rf_channels=len(regs), channel=channel, flags=r[2])
+
+    @staticmethod
+    def read_ls4_ini(text: str) -> dict:
+        """The [config] and [channel X] entries of the .ini beside a LabSat 4 (.ls4) recording that the reference reads (read_ls3w_ini with d_is_ls4,
+        gnuradio_blocks/labsat23_source.cc:700-920): QUA (else QUAN_A), CHN, SMP, BW_MAX, BW_DIV_A/B/C and BUF_SIZE_A/B/C -> dict(qua, chn, smp, bw_max,
+        bw_div [3], buf_size [3]).  ValueError for a QUA outside 1, 2, 4, 8, 12 (:716), CHN above 3 (:761), a BUF_SIZE that is not a multiple of 8 (:846)
+        and BUF_SIZE x BW_DIV that differ between the channels that have a buffer (:866-888)."""
+        import configparser
+        ini = configparser.ConfigParser(strict=False, interpolation=None)
+        ini.optionxform = str
+        ini.read_string(text)
+        if not ini.has_section("config"):
+            raise ValueError("the .ini of a LabSat 4 recording has no [config] section")
+        cfg = ini["config"]
+        qua = cfg.get("QUA") or cfg.get("QUAN_A")
+        if not qua:
+            raise ValueError("[config] has neither QUA nor QUAN_A")
+        qua, chn = int(qua), int(cfg.get("CHN") or 0)
+        if qua not in PackedFormat.LS4_QUA:
+            raise ValueError(f"QUA {qua}: a LabSat 4 sample quantization of 1, 2, 4, 8 or 12 bits is supported")
+        if not 1 <= chn <= 3:
+            raise ValueError(f"CHN {chn}: recordings of 1, 2 or 3 RF channels are supported")
+        bw_div, buf = [], []
+        for x in "ABC":
+            bw_div.append(int(cfg.get("BW_DIV_" + x) or 1))   # (the reference's default divisor is 1)
+            size = int(ini[f"channel {x}"].get("BUF_SIZE_" + x) or 0) if ini.has_section(f"channel {x}") else 0
+            if size > 0 and size % 8:
+                raise ValueError(f"BUF_SIZE_{x} {size} is not a multiple of 8")
+            buf.append(max(size, 0))
+        relative = {b * d for b, d in zip(buf, bw_div) if b * d > 0}   # (are_equal_ignore_nonpositive)
+        if len(relative) > 1:
+            raise ValueError(f"BUF_SIZE x BW_DIV differs between the channels ({', '.join(f'{b} x {d}' for b, d in zip(buf, bw_div) if b > 0)}): "
+                             "the buffer size configuration is invalid")
+        return dict(qua=qua, chn=chn, smp=float(cfg.get("SMP") or 0), bw_max=int(cfg.get("BW_MAX") or 0), bw_div=bw_div, buf_size=buf)
+
+    @classmethod
+    def from_ls4_ini(cls, text: str, selected_channel: int = 1) -> "PackedFormat":
+        """The format of a LabSat 4 (.ls4) recording from the text of the .ini beside it (read_ls4_ini).  regs[s] = BUF_SIZE_s / 8 for the three slots;
+        the single-channel calls take slot selected_channel - 1, which must lie within CHN (:932) and have a buffer."""
+        cfg = cls.read_ls4_ini(text)
+        sel = int(selected_channel)
+        if not 1 <= sel <= cfg["chn"]:
+            raise ValueError(f"selected_channel {sel}: the recording has {cfg['chn']} RF channel(s)")
+        if cfg["buf_size"][sel - 1] == 0:
+            raise ValueError(f"selected_channel {sel}: channel {'ABC'[sel - 1]} has no BUF_SIZE_{'ABC'[sel - 1]} in the .ini: it is not recorded")
+        return cls.ls4(cfg["qua"], [b // 8 for b in cfg["buf_size"]], sel - 1)
+
+    @property
+    def is_ls4(self) -> bool:
+        return self.LS4_1BIT <= self.family <= self.LS4_12BIT
+
+    @property
+    def ls4_qua(self) -> int:
+        return {v: k for k, v in self.LS4_QUA.items()}[self.family]
+
+    @property
+    def ls4_regs(self) -> "tuple[int, int, int]":
+        """registers of slots A, B, C per round of a LabSat 4 layout"""
+        return (self.big_endian_bytes, self.big_endian_items, self.flags)
+
+    @property
+    def ls4_round_bytes(self) -> int:
+        return 8 * sum(self.ls4_regs)
+
+    def ls4_samples_per_round(self, channel: int | None = None) -> int:
+        """samples of slot `channel` (default: the selected one) in one round: regs x 32 / QUA"""
+        return self.ls4_regs[self.channel if channel is None else channel] * 32 // self.ls4_qua
+
     def with_channel(self, channel: int) -> "PackedFormat":
         return PackedFormat(self.family, self.sample_type, self.item_size, self.big_endian_bytes, self.big_endian_items, self.rf_channels, channel,
                             self.flags)
 
     @property
     def is_register_family(self) -> bool:
-        return self.LABSAT_2BIT <= self.family <= self.SPIR_1BIT
+        return self.LABSAT_2BIT <= self.family <= self.SPIR_1BIT or self.is_ls4
 
     @property
     def is_complex(self) -> bool:
@@ -174,12 +259,17 @@ class PackedFormat:
     @property
     def item_bytes(self) -> int:
         """bytes of one input item: the 64-bit register of LS3W, the 16-bit item of LabSat 2 / 3, the 32-bit item of SPIR and word of GSS6450, the byte or
-        short of the other families"""
+        short of the other families.  LabSat 4 at QUA 12: the 24 bytes of a triple of registers, which hold samples_per_item = 8 whole samples"""
+        if self.family == self.LS4_12BIT:
+            return 24
         return self.item_size
 
     @property
     def samples_per_item(self) -> int:
-        """samples of one RF channel in one input item (LS3W: in one register, which holds as many of every RF channel)"""
+        """samples of one RF channel in one input item (LS3W: in one register, which holds as many of every RF channel; LS4: in one register of a
+        slot's buffer, at QUA 12 in one triple of registers)"""
+        if self.is_ls4:
+            return 8 if self.family == self.LS4_12BIT else 32 // self.ls4_qua
         if self.LS3W_1BIT <= self.family <= self.LS3W_3BIT:
             return self.LS3W_SAMPLES_PER_REGISTER[(self.family - self.LS3W_1BIT + 1, self.rf_channels)][self.flags & self.DIGITAL_IO]
         if self.is_register_family:
@@ -222,6 +312,8 @@ def _packed_host(fmt: PackedFormat, data, n_samples):
     a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data).view(np.uint8).reshape(-1)
     if n_samples is not None:
         return a, int(n_samples)
+    if fmt.is_ls4:   # whole rounds of the selected slot
+        return a, a.size // fmt.ls4_round_bytes * fmt.ls4_samples_per_round()
     if fmt.is_register_family:
         return a, a.size // fmt.item_bytes * fmt.samples_per_item
     n = a.size * fmt.samples_per_byte // fmt.interleaved_channels

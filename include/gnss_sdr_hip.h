@@ -413,12 +413,36 @@ extern "C"
      *                            bs[64 - start - i + 1], bit 65 - start - i: outside the 64-bit std::bitset for offsets 0 and 1 (undefined behaviour)
      *                            and elsewhere two bits above the position that the surrounding code implies (:1039 "Earlier samples are written in the
      *                            MSBs", the spare bits counted from the top, the LabSat 4 path taking "48 MSBs" with offsets 0 and 24).  This library
-     *                            reads bit 63 - start - i.  Not covered: LabSat 4, two-channel LabSat 2 / 3 files (refused by the reference, :496-500),
-     *                            and the host's file handling (the _0000.LS3 sequence, seconds_to_skip, throttling).
+     *                            reads bit 63 - start - i.  Not covered: two-channel LabSat 2 / 3 files (refused by the reference, :496-500) and
+     *                            throttling.  (The host's file handling -- the _0000.LS3 sequence, the .ini files, seconds_to_skip -- is the Python
+     *                            reader LabSatRecording.)
+     *   GSH_PACKED_LS4_1BIT      Labsat_Signal_Source, LabSat 4 (.ls4) with QUA = 1 / 2 / 4 / 8 / 12 bits each for I and Q (blocks/labsat23_source.cc:716;
+     *   GSH_PACKED_LS4_2BIT      :92-121 write_samples_ls4, :1262-1301 read_ls4_data / parse_ls4_data).  A LAYOUT is (QUA, regs[3]): regs[s] is the number
+     *   GSH_PACKED_LS4_4BIT      of 64-bit little-endian registers of channel slot s (A, B, C) per round, BUF_SIZE_s / 8 of the .ini (:836-857), 0 for a
+     *   GSH_PACKED_LS4_8BIT      slot that is not recorded.  The file is a run of ROUNDS: a round is the buffers of the recorded slots in the order A, B,
+     *   GSH_PACKED_LS4_12BIT     C, 8 x (regs[0] + regs[1] + regs[2]) bytes, and the buffers may differ in size (bandwidth divisors).  A packed block is
+     *                            a whole number of rounds and starts at a round boundary.  Inside one slot's buffer the registers form ONE bit stream,
+     *                            register 0 first, every register from its most significant bit down: sample j of the round starts at bit 2 QUA j, its
+     *                            I code is the first QUA bits, most significant first, its Q code the next QUA.  For QUA <= 8 a register holds 32 / QUA
+     *                            whole samples; at QUA 12 three registers hold 8 samples and samples 2 and 5 of such a triple straddle two registers
+     *                            (:92-121).  So slot s has S_s = regs[s] 32 / QUA samples per round, and its sample k lies in round k / S_s at j = k % S_s.
+     *                            Value: generate_mapping as for LS3W, half = 2^(QUA-1): code < half -> (code + 1) / half, else (code - 2^QUA) / half;
+     *                            every value is a multiple of 1 / half, exact in float32.  The reference requires BUF_SIZE_s BW_DIV_s to be equal over
+     *                            the slots (:866-888) and advances slot s by regs_per_output (div_selected / div_s) per output (:908-919,1262-1269), so
+     *                            every buffer of a round is used up at the same output: the format is defined by the layout alone and the descriptor
+     *                            carries no bandwidth divisor.  Descriptor: item_size 8, sample_type IQ, rf_channels = the slots described (1..3),
+     *                            channel = the selected slot (its regs > 0), and the three register counts in the fields that every other register
+     *                            family requires to be 0: big_endian_bytes = regs[A], big_endian_items = regs[B], reserved = regs[C] (0 .. 2^20 each, 0
+     *                            for a slot at or above rf_channels).  Sample counts are samples of the selected slot: whole registers (QUA <= 8) or
+     *                            whole triples (QUA 12); a count may end inside a round, and gsh_packed_bytes returns the bytes of the rounds touched.
+     *                            Multi-band as LS3W: one pass over the rounds writes up to three slots, which must hold EQUAL regs (the reference refuses
+     *                            to select channels of different bandwidth together, :898-906).  DEVIATIONS: bit i of a field at offset `start` is bit
+     *                            63 - start - i, as for LS3W; QUA 12 with regs[s] not a multiple of 3 is refused (the reference reads past the buffer
+     *                            there, :106-120 with data_index % data.size()).
      *   GSH_PACKED_SPIR_1BIT     Spir_File_Signal_Source (adapters/spir_file_signal_source.cc:50-58): blocks/unpack_intspir_1bit_samples.cc:36-68 with one
      *                            channel: one complex sample per 32-bit little-endian int, I = bit 0, Q = bit 1, +32767 when set and -32767 when clear.
-     * The six families above are complex (sample_type IQ), take big_endian_bytes = big_endian_items = 0, and their blocks are whole items / registers
-     * whose base is aligned to the item (2, 8 and 4 bytes).  The LS3W families are multi-band, as GSS6450.
+     * The eleven families above are complex (sample_type IQ), take big_endian_bytes = big_endian_items = 0 (LS4: its register counts instead), and their
+     * blocks are whole items / registers whose base is aligned to the item (2, 8, 8 and 4 bytes).  The LS3W and LS4 families are multi-band, as GSS6450.
      * The real families (TWO_BIT with sample_type real, NSR, NTLAB) are IF samples: they enter a ring through a packed FIR (gsh_fir_create_packed)
      * and gsh_stream_push_device, never directly.  Sample counts are samples of ONE RF channel and must be whole input items (the reference blocks
      * are sync_interpolators: they consume whole items).  Zero-initialise the descriptor and set what applies. */
@@ -435,25 +459,32 @@ extern "C"
 #define GSH_PACKED_LS3W_2BIT 11
 #define GSH_PACKED_LS3W_3BIT 12
 #define GSH_PACKED_SPIR_1BIT 13
+#define GSH_PACKED_LS4_1BIT 14
+#define GSH_PACKED_LS4_2BIT 15
+#define GSH_PACKED_LS4_4BIT 16
+#define GSH_PACKED_LS4_8BIT 17
+#define GSH_PACKED_LS4_12BIT 18
 #define GSH_PACKED_REAL 0 /* sample_type "real" */
 #define GSH_PACKED_IQ 1   /* sample_type "iq" */
 #define GSH_PACKED_QI 2   /* sample_type "qi" */
     typedef struct
     {
-        int32_t family;           /* GSH_PACKED_TWO_BIT .. GSH_PACKED_SPIR_1BIT (the SignalSource.implementation) */
+        int32_t family;           /* GSH_PACKED_TWO_BIT .. GSH_PACKED_LS4_12BIT (the SignalSource.implementation) */
         int32_t sample_type;      /* TWO_BIT: "sample_type", default real (two_bit_packed_file_signal_source.cc:39); FOUR_BIT_CPX: iq / qi, default iq
                                    * (four_bit_cpx_file_signal_source.cc:38); REAL for NSR and NTLAB; IQ for TWO_BIT_CPX */
         int32_t item_size;        /* TWO_BIT: 1 ("item_type" byte, the default of FileSourceBase) or 2 (short); GSS6450: 4 (the 32-bit word); LABSAT: 2;
-                                   * LS3W: 8 (the register); SPIR: 4; every other family: 1 */
-        int32_t big_endian_bytes; /* TWO_BIT: "big_endian_bytes", default false (two_bit_packed_file_signal_source.cc:41): sample order within a byte reversed */
+                                   * LS3W, LS4: 8 (the register); SPIR: 4; every other family: 1 */
+        int32_t big_endian_bytes; /* TWO_BIT: "big_endian_bytes", default false (two_bit_packed_file_signal_source.cc:41): sample order within a byte reversed;
+                                   * LS4: regs[A], the registers of slot A per round (BUF_SIZE_A / 8) */
         int32_t big_endian_items; /* TWO_BIT: "big_endian_items", default true (:40): with item_size 2 the two bytes of an item swap first; little-endian
                                    * short items are read as bytes (:63-77).  GSS6450: "endian", default false (spir_gss6450_file_signal_source.cc:51): the
-                                   * four bytes of every word are reversed before unpacking */
+                                   * four bytes of every word are reversed before unpacking.  LS4: regs[B], the registers of slot B per round */
         int32_t rf_channels;      /* NTLAB: "RF_channels", default 4 (ntlab_file_signal_source.cc:41-42), 4 only; GSS6450: "total_channels", 1..8 (0 reads as
-                                   * 1); LS3W: CHN, 1..3; every other family: 0 or 1 */
+                                   * 1); LS3W: CHN, 1..3; LS4: the channel slots described, 1..3; every other family: 0 or 1 */
         int32_t channel;          /* NTLAB: the RF channel unpacked by gsh_unpack_device / the packed FIR (0..3); GSS6450: the band the single-channel calls
-                                   * take, "sel_ch" - 1; LS3W: "selected_channel" - 1 (0..2); every other family: 0 */
-        int32_t reserved;         /* 0; LS3W: a flags word, bit 0 = digital I/O was recorded ("digital_io_enabled"), every other bit 0 */
+                                   * take, "sel_ch" - 1; LS3W: "selected_channel" - 1 (0..2); LS4: the selected slot (0..2, recorded); every other family: 0 */
+        int32_t reserved;         /* 0; LS3W: a flags word, bit 0 = digital I/O was recorded ("digital_io_enabled"), every other bit 0;
+                                   * LS4: regs[C], the registers of slot C per round */
     } gsh_packed_format;
     /* packed bytes that hold n_samples samples per RF channel; GSH_ERR_INVALID for a bad descriptor or a count that is not whole items.  No GPU. */
     int gsh_packed_bytes(const gsh_packed_format* fmt, uint64_t n_samples, uint64_t* bytes);
@@ -462,13 +493,13 @@ extern "C"
     int gsh_packed_decode_host(const gsh_packed_format* fmt, const void* bytes, uint64_t first_sample, uint64_t n_samples, float* out_iq);
     /* samples [first_sample, first_sample + n_samples) of the packed buffer d_src (sample 0 = the first of its first byte) -> d_dst: complex64 for
      * the complex families (conjugated when inverted_spectrum), float32 of fmt->channel for the real ones (inverted_spectrum must be 0).
-     * first_sample may fall inside a byte or a register, and n_samples need not end at one; d_src aligned to the item of a LABSAT / LS3W / SPIR family;
+     * first_sample may fall inside a byte or a register, and n_samples need not end at one; d_src aligned to the item of a LABSAT / LS3W / LS4 / SPIR family;
      * d_dst 8-byte aligned (complex) or 4-byte aligned (real).  Asynchronous on hip_stream. */
     int gsh_unpack_device(int device, const gsh_packed_format* fmt, const void* d_src, uint64_t first_sample, uint64_t n_samples, int inverted_spectrum,
         void* d_dst, void* hip_stream);
-    /* the same for several bands of a multi-band family (GSS6450, LS3W) in ONE pass over the packed block: samples [first_sample, first_sample + n_samples)
+    /* the same for several bands of a multi-band family (GSS6450, LS3W, LS4) in ONE pass over the packed block: samples [first_sample, first_sample + n_samples)
      * of band channels[i] -> complex64 at d_dst[i] (8-byte aligned), i < n_channels <= rf_channels.  fmt->channel is not consulted.  GSH_ERR_INVALID
-     * for a family without several bands, a band out of range or named twice, a null or misaligned destination.  d_src is 4-byte aligned (GSS6450) or 8-byte aligned (LS3W).
+     * for a family without several bands, a band out of range or named twice, a null or misaligned destination.  d_src is 4-byte aligned (GSS6450) or 8-byte aligned (LS3W, LS4).  The LS4 slots of one call hold equal register counts.
      * Asynchronous on hip_stream. */
     int gsh_unpack_device_multi(int device, const gsh_packed_format* fmt, const void* d_src, uint64_t first_sample, uint64_t n_samples,
         int inverted_spectrum, const int32_t* channels, int n_channels, void* const* d_dst, void* hip_stream);
@@ -480,7 +511,7 @@ extern "C"
         void* hip_stream, uint64_t* first_index);
     int gsh_stream_push_packed_pinned_async(gsh_stream_t* s, const gsh_packed_format* fmt, const void* bytes, uint64_t n_samples, int inverted_spectrum,
         uint64_t* first_index);
-    /* One push of a multi-band packed block (GSS6450, LS3W) into n_rings rings: band channels[i] goes to rings[i].  The block crosses PCIe once and
+    /* One push of a multi-band packed block (GSS6450, LS3W, LS4) into n_rings rings: band channels[i] goes to rings[i].  The block crosses PCIe once and
      * one pass over it writes every ring; afterwards each ring is, bit for bit and index for index, what the single-ring call of the same name
      * with fmt->channel = channels[i] would have left (resident range, mirror, push event, live words), and gsh_stream_wait / _wait_copied /
      * _wait_copied_upto work on every ring of the call.  Rings may differ in capacity, window and next index; they lie on one device.  n_samples
