@@ -281,22 +281,25 @@ CondArgs block_args(const gsh_cond* h, const void* d_block, unsigned long long n
     return a;
 }
 
+// what the segments of a push share; a push with a stage adds what its gather needs (BlankSegmentCtx, NotchSegmentCtx) and launches that instead
 struct SegmentCtx
 {
     CondArgs a;                      // of the whole push
     unsigned long long out0;         // absolute output index of the push's first ring sample
+    int launch(const CondArgs& seg, hipStream_t st) const { return gsh::cond_launch(seg, st); }
 };
 
-// MultiSegmentWriter: ring samples [first, first + len) of the push into dst[0]
+// MultiSegmentWriter: ring samples [first, first + len) of the push into dst[0], by the launcher of the push's context
+template <class Ctx>
 int write_segment(void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t st)
 {
-    const SegmentCtx* c = static_cast<const SegmentCtx*>(ctx);
+    const Ctx* c = static_cast<const Ctx*>(ctx);
     CondArgs a = c->a;
     a.out = dst[0];
     a.out0 = c->out0 + first;
     a.n_out = len;
     gsh::cond_plan_resampler(&a);
-    return gsh::cond_launch(a, st);
+    return c->launch(a, st);
 }
 
 int grow(void** buf, size_t* cap, size_t bytes)
@@ -375,24 +378,14 @@ int blank_stage(const gsh_cond* h, const CondArgs& block, const BlankFrame& f, g
     return GSH_OK;
 }
 
+// SegmentCtx of a push with the blanking stage
 struct BlankSegmentCtx
 {
     CondArgs a;
     unsigned long long out0;
     gsh::CondBlankArgs b;
+    int launch(const CondArgs& seg, hipStream_t st) const { return gsh::cond_blank_launch_gather(seg, b, st); }
 };
-
-// MultiSegmentWriter of a push with the blanking stage
-int write_segment_blanked(void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t st)
-{
-    const BlankSegmentCtx* c = static_cast<const BlankSegmentCtx*>(ctx);
-    CondArgs a = c->a;
-    a.out = dst[0];
-    a.out0 = c->out0 + first;
-    a.n_out = len;
-    gsh::cond_plan_resampler(&a);
-    return gsh::cond_blank_launch_gather(a, c->b, st);
-}
 
 NotchFrame notch_frame(const gsh_cond* h, unsigned long long n_in)
 {
@@ -498,38 +491,31 @@ int notch_stage(const gsh_cond* h, const CondArgs& block, const NotchFrame& f, g
     return gsh::cond_notch_launch_save(*n, st);
 }
 
+// SegmentCtx of a push with the notch stage
 struct NotchSegmentCtx
 {
     CondArgs a;
     unsigned long long out0;
     gsh::CondNotchArgs n;
+    int launch(const CondArgs& seg, hipStream_t st) const { return gsh::cond_notch_launch_gather(seg, n, st); }
 };
 
-// MultiSegmentWriter of a push with the notch stage
-int write_segment_notched(void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t st)
+// What every push shares, around its stage's own launches.  Before anything is queued: st comes behind the latest push's device work, which wrote the
+// history (and the stage's carry) this one reads ...
+int await_history(const gsh_cond* h, hipStream_t st)
 {
-    const NotchSegmentCtx* c = static_cast<const NotchSegmentCtx*>(ctx);
-    CondArgs a = c->a;
-    a.out = dst[0];
-    a.out0 = c->out0 + first;
-    a.n_out = len;
-    gsh::cond_plan_resampler(&a);
-    return gsh::cond_notch_launch_gather(a, c->n, st);
+    if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
+    return GSH_OK;
 }
 
-int push_block_blanked(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st);
-int push_block_notched(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st);
-
-// queue the device work of a checked push on st and advance the handle
-int push_block(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st)
+// ... and behind the stage: the push's ring samples by its context's launcher, the new history tail into the other half, the event the next push
+// waits for, the totals
+template <class Ctx>
+int write_and_advance(gsh_cond* h, Ctx& ctx, unsigned long long n_in, unsigned long long count, hipStream_t st)
 {
-    if (h->blank_on) return push_block_blanked(h, d_block, n_in, count, st);
-    if (h->notch_on) return push_block_notched(h, d_block, n_in, count, st);
-    if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
-    SegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total};
     if (count > 0)
         {
-            int rc = gsh::stream_write_device_multi(&h->ring, 1, count, st, write_segment, &ctx);
+            int rc = gsh::stream_write_device_multi(&h->ring, 1, count, st, write_segment<Ctx>, &ctx);
             if (rc != GSH_OK) return rc;
         }
     if (n_in > 0)
@@ -552,30 +538,13 @@ int push_block_blanked(gsh_cond* h, const void* d_block, unsigned long long n_in
 {
     const BlankFrame f = blank_frame(h, n_in);
     int rc = blank_reserve(h, f);
+    if (rc == GSH_OK) rc = await_history(h, st);
     if (rc != GSH_OK) return rc;
-    if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
     BlankSegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total, {}};
     rc = blank_stage(h, ctx.a, f, h->d_bstate, st, &ctx.b);
+    if (rc == GSH_OK) rc = write_and_advance(h, ctx, n_in, count, st);
     if (rc != GSH_OK) return rc;
-    if (count > 0)
-        {
-            rc = gsh::stream_write_device_multi(&h->ring, 1, count, st, write_segment_blanked, &ctx);
-            if (rc != GSH_OK) return rc;
-        }
-    if (n_in > 0)
-        {
-            if (h->plan.n_taps > 1)
-                {
-                    rc = gsh::cond_launch_history(ctx.a, st);
-                    if (rc != GSH_OK) return rc;
-                    h->cur ^= 1;
-                }
-            GSH_HIP(hipEventRecord(h->hist_ev, st));
-            h->hist_recorded = true;
-        }
     if (f.c1 > 0) h->carry_cur ^= 1;
-    h->n_in_total += n_in;
-    h->n_out_total += count;
     return GSH_OK;
 }
 
@@ -583,31 +552,25 @@ int push_block_notched(gsh_cond* h, const void* d_block, unsigned long long n_in
 {
     const NotchFrame f = notch_frame(h, n_in);
     int rc = notch_reserve(h, f);
+    if (rc == GSH_OK) rc = await_history(h, st);
     if (rc != GSH_OK) return rc;
-    if (h->hist_recorded) GSH_HIP(hipStreamWaitEvent(st, h->hist_ev, 0));
     NotchSegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total, {}};
     rc = notch_stage(h, ctx.a, f, h->d_nstate, st, &ctx.n);
+    if (rc == GSH_OK) rc = write_and_advance(h, ctx, n_in, count, st);
     if (rc != GSH_OK) return rc;
-    if (count > 0)
-        {
-            rc = gsh::stream_write_device_multi(&h->ring, 1, count, st, write_segment_notched, &ctx);
-            if (rc != GSH_OK) return rc;
-        }
-    if (n_in > 0)
-        {
-            if (h->plan.n_taps > 1)
-                {
-                    rc = gsh::cond_launch_history(ctx.a, st);
-                    if (rc != GSH_OK) return rc;
-                    h->cur ^= 1;
-                }
-            GSH_HIP(hipEventRecord(h->hist_ev, st));
-            h->hist_recorded = true;
-        }
     h->notch_cur ^= 1;  // (the save wrote the other halves, an unchanged carry included)
-    h->n_in_total += n_in;
-    h->n_out_total += count;
     return GSH_OK;
+}
+
+// queue the device work of a checked push on st and advance the handle
+int push_block(gsh_cond* h, const void* d_block, unsigned long long n_in, unsigned long long count, hipStream_t st)
+{
+    if (h->blank_on) return push_block_blanked(h, d_block, n_in, count, st);
+    if (h->notch_on) return push_block_notched(h, d_block, n_in, count, st);
+    int rc = await_history(h, st);
+    if (rc != GSH_OK) return rc;
+    SegmentCtx ctx{block_args(h, d_block, n_in), h->n_out_total};
+    return write_and_advance(h, ctx, n_in, count, st);
 }
 
 void report(const gsh_cond* h, unsigned long long count, uint64_t* first_out, uint64_t* n_out)

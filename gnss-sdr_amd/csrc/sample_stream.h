@@ -65,7 +65,8 @@ struct gsh_stream
     // to wait for the launch it held, and `read_fold` (recorded on the ring's stream right after) stands for all of them -- every push waits on it
     hipEvent_t read_fold{nullptr};
     bool has_fold{false};
-    // gsh_stream_push_staged: page-locked host staging + device staging, four in rotation
+    // page-locked host staging + device staging, four pairs in one rotation (stage_slot, sample_stream.hip) for gsh_stream_push_staged, _push_pinned_async
+    // and the packed pinned pushes
     static constexpr int NSTAGE = 4;
     void* h_stage[NSTAGE]{};
     void* d_stage[NSTAGE]{};
@@ -94,10 +95,10 @@ inline unsigned long long stream_oldest(const gsh_stream* s)
 int stream_mark_read(gsh_stream* s, unsigned long long min_index, hipStream_t st);
 // make `st` wait until samples below `need_end` are in the ring (need_end = ~0ull: everything pushed so far)
 int stream_wait_pushed(gsh_stream* s, unsigned long long need_end, hipStream_t st);
-// queue the conversion of n raw items at d_src (device memory) into ring positions [next, next + n) on the ring's own stream, after the readers'
-// fences; records `pushed` and advances `next`
+// queue the conversion of n raw items at d_src (device memory) into ring positions [next, next + n) on st, after the readers' fences; records the push
+// event, publishes the live words and advances `next` (the whole of gsh_stream_push_device but its argument checks and its wait)
 int stream_write_device_items(gsh_stream* s, const void* d_src, unsigned long long n, int item_type, int conj, hipStream_t st);
-// the same for n packed complex samples at d_src (sample 0 at its first byte)
+// the same for n packed complex samples at d_src (sample 0 at its first byte): one body with the above
 int stream_write_device_packed(gsh_stream* s, const void* d_src, const PackedCode& c, unsigned long long n, int conj, hipStream_t st);
 // the same for several rings at once: band channels[i] of the multi-band packed block at d_src -> ring rings[i], one pass over the block (the caller
 // has validated rings, bands and n; every ring's reader fences, mirror, push event and live words are kept as by the single-ring call)

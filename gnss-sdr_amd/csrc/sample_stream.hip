@@ -1,5 +1,16 @@
 // gsh_stream_*: the IF sample stream of one front-end as a ring in device memory, addressed by absolute sample index.
 // See include/gnss_sdr_hip.h for the contract and the reference pieces it stands in for.
+//
+// Every single-ring push entry is a short sequence of the same steps, each written once below:
+//     check_item_push / check_packed_push   the arguments, in the order their errors are reported
+//     open_push                             *first_index, the return of an empty push, the ring's device
+//     stream_raw_staging / stage_slot / raw2_slot   where the block lands on the device: the one raw buffer of the synchronous pushes, the next of the
+//                                           four staging pairs (staged, pinned, packed pinned), the other of gsh_stream_push_async's two buffers
+//     direct_dma                            whether page-locked items go straight into their ring positions instead
+//     write_items                           the frame of a single-ring write: live floor, reader fences, conversion piece by piece, mirror
+//     commit_push / commit_staged           the staging pair's event, the push event, the live words, then `next`
+// so within a push its stream sees copies and conversion, mirror copy, the staging slot's event, the push event, publish_live_kernel, in that order, and
+// the host advances `next` last.  The multi-ring pushes have their own frame, stream_write_device_multi, which orders the rings' streams as well.
 #include "sample_stream.h"
 #include "packed_unpack.h"
 #include "sample_convert.h"
@@ -118,14 +129,16 @@ namespace
 {
 using gsh::set_error;
 
-// GSH_STREAM_DIRECT_DMA=0: page-locked gr_complex items go through the device staging buffer like every other item type (the path of rounds 2-3, for A/B runs)
-bool stream_direct_dma()
+// page-locked gr_complex items that need no conversion are the ring's own format: the DMA's destination is the ring itself
+// (profiles/ab/r03/dropin_direct_dma.txt).  GSH_STREAM_DIRECT_DMA=0: they go through the device staging buffer like every other item type (the path of
+// rounds 2-3, for A/B runs)
+bool direct_dma(int item_type, int inverted_spectrum)
 {
     static const bool on = [] {
         const char* e = std::getenv("GSH_STREAM_DIRECT_DMA");
         return e == nullptr || std::atoi(e) != 0;
     }();
-    return on;
+    return item_type == GSH_ITEM_GR_COMPLEX && !inverted_spectrum && on;
 }
 
 // a staging buffer that has been outgrown.  hipFree waits for the WHOLE device -- with a live loop resident on it (tracking_loop.hip) that is until the
@@ -168,10 +181,10 @@ int wait_for_readers(gsh_stream* s, unsigned long long n, hipStream_t st)
 }
 
 // queue the conversion of n items at d_src into ring positions of absolute indices [first, first + n) on `st`.  host_src: d_src is page-locked HOST memory
-// holding gr_complex items to be taken as they are -- the ring positions are then the destination of the DMA itself (no staging buffer, no second copy);
-// *copied_after (an event), when given, is recorded behind the last read of d_src.  packed: d_src holds packed complex samples of that format (item_type
-// unused), sample 0 at its first byte; a segment that starts inside a byte is unpacked from its first-sample offset.
-int write_items(gsh_stream* s, const void* d_src, unsigned long long n, int item_type, int conj, hipStream_t st, bool host_src = false, hipEvent_t copied_after = nullptr,
+// holding gr_complex items to be taken as they are -- the ring positions are then the destination of the DMA itself (no staging buffer, no second copy).
+// packed: d_src holds packed complex samples of that format (item_type unused), sample 0 at its first byte; a segment that starts inside a byte is
+// unpacked from its first-sample offset.
+int write_items(gsh_stream* s, const void* d_src, unsigned long long n, int item_type, int conj, hipStream_t st, bool host_src = false,
     const gsh::PackedCode* packed = nullptr)
 {
     const size_t isz = gsh::item_bytes(item_type);
@@ -187,10 +200,7 @@ int write_items(gsh_stream* s, const void* d_src, unsigned long long n, int item
             const unsigned long long len = std::min(n - done, C - p);
             const char* src = static_cast<const char*>(d_src) + done * isz;
             if (host_src)
-                {
-                    GSH_HIP(hipMemcpyAsync(s->d_ring + p, src, sizeof(float2) * len, hipMemcpyHostToDevice, st));
-                    if (done + len == n && copied_after != nullptr) GSH_HIP(hipEventRecord(copied_after, st));  // (before the mirror copy: that one reads the ring)
-                }
+                GSH_HIP(hipMemcpyAsync(s->d_ring + p, src, sizeof(float2) * len, hipMemcpyHostToDevice, st));
             else if (packed != nullptr)
                 {
                     int rc = gsh::unpack_packed(d_src, *packed, done, len, conj, s->d_ring + p, st);
@@ -210,10 +220,7 @@ int write_items(gsh_stream* s, const void* d_src, unsigned long long n, int item
         }
     return GSH_OK;
 }
-}  // namespace
 
-namespace
-{
 // after a push's device work has been queued on `st`: the "latest" event and the (end index, event) history entry
 int record_push(gsh_stream* s, unsigned long long end_index, hipStream_t st)
 {
@@ -230,28 +237,38 @@ int record_push(gsh_stream* s, unsigned long long end_index, hipStream_t st)
     }
     return gsh::stream_publish_live(s, end_index, st);
 }
+
+// the end of every single-ring push, behind its device work on `st`: the push event and the live words, then `next`.  synchronous: the host waits for
+// `st` in between (gsh_stream_push, gsh_stream_push_packed) and `next` stays where it was when that wait fails
+int commit_push(gsh_stream* s, unsigned long long n, hipStream_t st, bool synchronous = false)
+{
+    int rc = record_push(s, s->next + n, st);
+    if (rc != GSH_OK) return rc;
+    if (synchronous) GSH_HIP(hipStreamSynchronize(st));
+    s->next += n;
+    return GSH_OK;
+}
+
+// a push whose source needs nothing but the write: write_items, then the commit
+int write_and_commit(gsh_stream* s, const void* d_src, unsigned long long n, int item_type, int conj, hipStream_t st, bool host_src = false,
+    const gsh::PackedCode* packed = nullptr)
+{
+    int rc = write_items(s, d_src, n, item_type, conj, st, host_src, packed);
+    if (rc != GSH_OK) return rc;
+    return commit_push(s, n, st);
+}
 }  // namespace
 
 namespace gsh
 {
 int stream_write_device_items(gsh_stream* s, const void* d_src, unsigned long long n, int item_type, int conj, hipStream_t st)
 {
-    int rc = write_items(s, d_src, n, item_type, conj, st);
-    if (rc != GSH_OK) return rc;
-    rc = record_push(s, s->next + n, st);
-    if (rc != GSH_OK) return rc;
-    s->next += n;
-    return GSH_OK;
+    return write_and_commit(s, d_src, n, item_type, conj, st);
 }
 
 int stream_write_device_packed(gsh_stream* s, const void* d_src, const PackedCode& c, unsigned long long n, int conj, hipStream_t st)
 {
-    int rc = write_items(s, d_src, n, GSH_ITEM_BYTE, conj, st, false, nullptr, &c);
-    if (rc != GSH_OK) return rc;
-    rc = record_push(s, s->next + n, st);
-    if (rc != GSH_OK) return rc;
-    s->next += n;
-    return GSH_OK;
+    return write_and_commit(s, d_src, n, GSH_ITEM_BYTE, conj, st, false, &c);
 }
 
 int stream_write_device_multi(gsh_stream* const* rings, int n_rings, unsigned long long n, hipStream_t st, MultiSegmentWriter write, void* ctx)
@@ -378,8 +395,42 @@ int packed_ring_format(const gsh_packed_format* fmt, unsigned long long n, Packe
 
 namespace
 {
-// the next of the ring's four staging pairs, free again (the unpack that read its device buffer four pushes ago has finished) and at least nbytes long
-int packed_stage_slot(gsh_stream* s, size_t nbytes, int* out)
+// the arguments of a single-ring push of items, in the order every entry reports them
+int check_item_push(const gsh_stream* s, const void* items, unsigned long long n, int item_type)
+{
+    GSH_REQUIRE(s != nullptr, "null stream");
+    GSH_REQUIRE(n == 0 || items != nullptr, "null items");
+    GSH_REQUIRE(gsh::item_bytes(item_type) != 0, "unknown item type %d", item_type);
+    GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", n, s->capacity);
+    return GSH_OK;
+}
+
+// the same for packed complex samples: *c = the reduced format, *nbytes = the size of the block
+int check_packed_push(const gsh_stream* s, const gsh_packed_format* fmt, const void* bytes, unsigned long long n, gsh::PackedCode* c, unsigned long long* nbytes)
+{
+    GSH_REQUIRE(s != nullptr, "null stream");
+    GSH_REQUIRE(n == 0 || bytes != nullptr, "null items");
+    int rc = gsh::packed_ring_format(fmt, n, c, nbytes);
+    if (rc != GSH_OK) return rc;
+    GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", n, s->capacity);
+    return GSH_OK;
+}
+
+// a checked push opens: *first_index is written (for an empty push too, and before any HIP call), then the ring's device is selected.  false: the entry
+// returns *rc -- GSH_OK for an empty push, the error otherwise
+bool open_push(gsh_stream* s, unsigned long long n, uint64_t* first_index, int* rc)
+{
+    if (first_index) *first_index = s->next;
+    *rc = GSH_OK;
+    if (n == 0) return false;
+    const hipError_t e = hipSetDevice(s->device);
+    if (e != hipSuccess) *rc = gsh::hip_fail(e, "hipSetDevice(s->device)", __FILE__, __LINE__);
+    return e == hipSuccess;
+}
+
+// the next of the ring's four staging pairs (page-locked host buffer + device buffer, shared by the staged, the pinned and the packed pinned pushes),
+// free again -- the device work that read it four pushes ago has finished -- and at least nbytes long
+int stage_slot(gsh_stream* s, size_t nbytes, int* out)
 {
     const int slot = s->stage_next;
     s->stage_next = (s->stage_next + 1) % gsh_stream::NSTAGE;
@@ -395,9 +446,36 @@ int packed_stage_slot(gsh_stream* s, size_t nbytes, int* out)
             s->d_stage[slot] = nullptr;
             s->stage_cap[slot] = 0;
             const size_t cap = nbytes + nbytes / 2;
-            GSH_HIP(hipHostMalloc(&s->h_stage[slot], cap, hipHostMallocDefault));  // (kept in step with the staged path, which shares the slots)
+            GSH_HIP(hipHostMalloc(&s->h_stage[slot], cap, hipHostMallocDefault));
             GSH_HIP(hipMalloc(&s->d_stage[slot], cap));
             s->stage_cap[slot] = cap;
+        }
+    *out = slot;
+    return GSH_OK;
+}
+
+// behind the device work that read staging pair `slot` on the ring's stream: the pair's event, then the commit
+int commit_staged(gsh_stream* s, int slot, unsigned long long n)
+{
+    GSH_HIP(hipEventRecord(s->stage_done[slot], s->stream));
+    return commit_push(s, n, s->stream);
+}
+
+// gsh_stream_push_async's own rotation: the other of two device buffers, nbytes long.  Unlike the four-slot rotation it waits only when it grows -- the
+// previous conversion out of the slot, two pushes ago, ran on the same stream as the copy that follows -- and it allocates the exact size
+int raw2_slot(gsh_stream* s, size_t nbytes, int* out)
+{
+    const int slot = s->raw2_next;
+    s->raw2_next ^= 1;
+    if (s->raw2_done[slot] == nullptr) GSH_HIP(hipEventCreateWithFlags(&s->raw2_done[slot], hipEventDisableTiming));
+    if (nbytes > s->raw2_cap[slot])
+        {
+            GSH_HIP(hipEventSynchronize(s->raw2_done[slot]));  // nothing queued may still read the buffer being replaced
+            if (s->d_raw2[slot]) GSH_HIP(release_buffer(s, s->d_raw2[slot], false));
+            s->d_raw2[slot] = nullptr;
+            s->raw2_cap[slot] = 0;
+            GSH_HIP(hipMalloc(&s->d_raw2[slot], nbytes));
+            s->raw2_cap[slot] = nbytes;
         }
     *out = slot;
     return GSH_OK;
@@ -525,50 +603,28 @@ extern "C"
     int gsh_stream_push_device(gsh_stream_t* s, const void* device_items, uint64_t n, int item_type, int inverted_spectrum, void* hip_stream,
         uint64_t* first_index)
     {
-        GSH_REQUIRE(s != nullptr, "null stream");
-        GSH_REQUIRE(n == 0 || device_items != nullptr, "null items");
-        GSH_REQUIRE(gsh::item_bytes(item_type) != 0, "unknown item type %d", item_type);
-        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
-        if (first_index) *first_index = s->next;
-        if (n == 0) return GSH_OK;
-        GSH_HIP(hipSetDevice(s->device));
+        int rc = check_item_push(s, device_items, n, item_type);
+        if (rc != GSH_OK) return rc;
+        if (!open_push(s, n, first_index, &rc)) return rc;
         hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
-        int rc = write_items(s, device_items, n, item_type, inverted_spectrum ? 1 : 0, st);
+        rc = gsh::stream_write_device_items(s, device_items, n, item_type, inverted_spectrum ? 1 : 0, st);
         if (rc != GSH_OK) return rc;
-        rc = record_push(s, s->next + n, st);
-        if (rc != GSH_OK) return rc;
-        s->next += n;
         if (!hip_stream) GSH_HIP(hipStreamSynchronize(st));
         return GSH_OK;
     }
 
     int gsh_stream_push(gsh_stream_t* s, const void* items, uint64_t n, int item_type, int inverted_spectrum, uint64_t* first_index)
     {
-        GSH_REQUIRE(s != nullptr, "null stream");
-        GSH_REQUIRE(n == 0 || items != nullptr, "null items");
-        const size_t isz = gsh::item_bytes(item_type);
-        GSH_REQUIRE(isz != 0, "unknown item type %d", item_type);
-        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
-        if (first_index) *first_index = s->next;
-        if (n == 0) return GSH_OK;
-        GSH_HIP(hipSetDevice(s->device));
-        const size_t bytes = static_cast<size_t>(n) * isz;
-        if (bytes > s->raw_cap)
-            {
-                if (s->d_raw) GSH_HIP(release_buffer(s, s->d_raw, false));
-                s->d_raw = nullptr;
-                s->raw_cap = 0;
-                GSH_HIP(hipMalloc(&s->d_raw, bytes));
-                s->raw_cap = bytes;
-            }
+        int rc = check_item_push(s, items, n, item_type);
+        if (rc != GSH_OK) return rc;
+        if (!open_push(s, n, first_index, &rc)) return rc;
+        const size_t bytes = static_cast<size_t>(n) * gsh::item_bytes(item_type);
+        rc = gsh::stream_raw_staging(s, bytes);
+        if (rc != GSH_OK) return rc;
         GSH_HIP(hipMemcpyAsync(s->d_raw, items, bytes, hipMemcpyHostToDevice, s->stream));
-        int rc = write_items(s, s->d_raw, n, item_type, inverted_spectrum ? 1 : 0, s->stream);
+        rc = write_items(s, s->d_raw, n, item_type, inverted_spectrum ? 1 : 0, s->stream);
         if (rc != GSH_OK) return rc;
-        rc = record_push(s, s->next + n, s->stream);
-        if (rc != GSH_OK) return rc;
-        GSH_HIP(hipStreamSynchronize(s->stream));
-        s->next += n;
-        return GSH_OK;
+        return commit_push(s, n, s->stream, true);
     }
 
     int gsh_stream_push_async(gsh_stream_t* s, const void* items, uint64_t n, int item_type, int inverted_spectrum, uint64_t* first_index)
@@ -576,36 +632,18 @@ extern "C"
         // H2D copy + conversion queued on the ring's stream; returns without waiting.  Two device staging buffers alternate, so the copy of
         // block k + 1 can run while the conversion of block k still reads its staging buffer, and -- the point of it -- while the
         // correlators work on block k on their own streams (they wait on `pushed`, not on the host).
-        GSH_REQUIRE(s != nullptr, "null stream");
-        GSH_REQUIRE(n == 0 || items != nullptr, "null items");
-        const size_t isz = gsh::item_bytes(item_type);
-        GSH_REQUIRE(isz != 0, "unknown item type %d", item_type);
-        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
-        if (first_index) *first_index = s->next;
-        if (n == 0) return GSH_OK;
-        GSH_HIP(hipSetDevice(s->device));
-        const int slot = s->raw2_next;
-        s->raw2_next ^= 1;
-        const size_t bytes = static_cast<size_t>(n) * isz;
-        if (s->raw2_done[slot] == nullptr) GSH_HIP(hipEventCreateWithFlags(&s->raw2_done[slot], hipEventDisableTiming));
-        if (bytes > s->raw2_cap[slot])
-            {
-                GSH_HIP(hipEventSynchronize(s->raw2_done[slot]));  // nothing queued may still read the buffer being replaced
-                if (s->d_raw2[slot]) GSH_HIP(release_buffer(s, s->d_raw2[slot], false));
-                s->d_raw2[slot] = nullptr;
-                s->raw2_cap[slot] = 0;
-                GSH_HIP(hipMalloc(&s->d_raw2[slot], bytes));
-                s->raw2_cap[slot] = bytes;
-            }
-        // same stream as the previous conversion out of this slot (two pushes ago): ordered without an explicit wait
+        int rc = check_item_push(s, items, n, item_type);
+        if (rc != GSH_OK) return rc;
+        if (!open_push(s, n, first_index, &rc)) return rc;
+        const size_t bytes = static_cast<size_t>(n) * gsh::item_bytes(item_type);
+        int slot = 0;
+        rc = raw2_slot(s, bytes, &slot);
+        if (rc != GSH_OK) return rc;
         GSH_HIP(hipMemcpyAsync(s->d_raw2[slot], items, bytes, hipMemcpyHostToDevice, s->stream));
-        int rc = write_items(s, s->d_raw2[slot], n, item_type, inverted_spectrum ? 1 : 0, s->stream);
+        rc = write_items(s, s->d_raw2[slot], n, item_type, inverted_spectrum ? 1 : 0, s->stream);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipEventRecord(s->raw2_done[slot], s->stream));
-        rc = record_push(s, s->next + n, s->stream);
-        if (rc != GSH_OK) return rc;
-        s->next += n;
-        return GSH_OK;
+        return commit_push(s, n, s->stream);
     }
 
     int gsh_stream_push_staged(gsh_stream_t* s, const void* items, uint64_t n, int item_type, int inverted_spectrum, uint64_t* first_index)
@@ -613,52 +651,21 @@ extern "C"
         // items -> page-locked staging (host memcpy: the caller's buffer is free on return, whatever kind of memory it is) -> the ring.  gr_complex items that
         // need no conversion are copied by the DMA engine straight from the staging buffer into their ring positions; every other item type goes
         // staging -> device staging -> conversion kernel.  A staging pair is re-used four pushes later, after the device work that read it has finished.
-        GSH_REQUIRE(s != nullptr, "null stream");
-        GSH_REQUIRE(n == 0 || items != nullptr, "null items");
-        const size_t isz = gsh::item_bytes(item_type);
-        GSH_REQUIRE(isz != 0, "unknown item type %d", item_type);
-        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
-        if (first_index) *first_index = s->next;
-        if (n == 0) return GSH_OK;
-        GSH_HIP(hipSetDevice(s->device));
-        const int slot = s->stage_next;
-        s->stage_next = (s->stage_next + 1) % gsh_stream::NSTAGE;
-        const size_t bytes = static_cast<size_t>(n) * isz;
-        if (s->stage_done[slot] == nullptr)
-            GSH_HIP(hipEventCreateWithFlags(&s->stage_done[slot], hipEventDisableTiming));
-        else
-            GSH_HIP(hipEventSynchronize(s->stage_done[slot]));  // the push that used this pair four pushes ago
-        if (bytes > s->stage_cap[slot])
-            {
-                if (s->h_stage[slot]) GSH_HIP(release_buffer(s, s->h_stage[slot], true));
-                if (s->d_stage[slot]) GSH_HIP(release_buffer(s, s->d_stage[slot], false));
-                s->h_stage[slot] = nullptr;
-                s->d_stage[slot] = nullptr;
-                s->stage_cap[slot] = 0;
-                const size_t cap = bytes + bytes / 2;
-                GSH_HIP(hipHostMalloc(&s->h_stage[slot], cap, hipHostMallocDefault));
-                GSH_HIP(hipMalloc(&s->d_stage[slot], cap));
-                s->stage_cap[slot] = cap;
-            }
+        int rc = check_item_push(s, items, n, item_type);
+        if (rc != GSH_OK) return rc;
+        if (!open_push(s, n, first_index, &rc)) return rc;
+        const size_t bytes = static_cast<size_t>(n) * gsh::item_bytes(item_type);
+        int slot = 0;
+        rc = stage_slot(s, bytes, &slot);
+        if (rc != GSH_OK) return rc;
         std::memcpy(s->h_stage[slot], items, bytes);
-        int rc;
-        if (item_type == GSH_ITEM_GR_COMPLEX && !inverted_spectrum && stream_direct_dma())
-            {
-                // the ring's own format: the DMA's destination is the ring (profiles/ab/r03/dropin_direct_dma.txt); its SOURCE is the page-locked staging
-                // copy, never the caller's pageable buffer (an asynchronous copy out of pageable memory is only safe if the runtime happens to stage it itself)
-                rc = write_items(s, s->h_stage[slot], n, item_type, 0, s->stream, true, nullptr);
-            }
-        else
-            {
-                GSH_HIP(hipMemcpyAsync(s->d_stage[slot], s->h_stage[slot], bytes, hipMemcpyHostToDevice, s->stream));
-                rc = write_items(s, s->d_stage[slot], n, item_type, inverted_spectrum ? 1 : 0, s->stream);
-            }
+        // the direct DMA's SOURCE is the page-locked staging copy, never the caller's pageable buffer (an asynchronous copy out of pageable memory is only
+        // safe if the runtime happens to stage it itself)
+        const bool direct = direct_dma(item_type, inverted_spectrum);
+        if (!direct) GSH_HIP(hipMemcpyAsync(s->d_stage[slot], s->h_stage[slot], bytes, hipMemcpyHostToDevice, s->stream));
+        rc = write_items(s, direct ? s->h_stage[slot] : s->d_stage[slot], n, item_type, inverted_spectrum ? 1 : 0, s->stream, direct);
         if (rc != GSH_OK) return rc;
-        GSH_HIP(hipEventRecord(s->stage_done[slot], s->stream));
-        rc = record_push(s, s->next + n, s->stream);
-        if (rc != GSH_OK) return rc;
-        s->next += n;
-        return GSH_OK;
+        return commit_staged(s, slot, n);
     }
 
     int gsh_stream_wait_copied(gsh_stream_t* s)
@@ -707,99 +714,46 @@ extern "C"
     int gsh_stream_push_pinned_async(gsh_stream_t* s, const void* items, uint64_t n, int item_type, int inverted_spectrum, uint64_t* first_index)
     {
         // page-locked items -> device staging (DMA straight out of the caller's memory) -> conversion into the ring; nothing waits here
-        GSH_REQUIRE(s != nullptr, "null stream");
-        GSH_REQUIRE(n == 0 || items != nullptr, "null items");
-        const size_t isz = gsh::item_bytes(item_type);
-        GSH_REQUIRE(isz != 0, "unknown item type %d", item_type);
-        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
-        if (first_index) *first_index = s->next;
-        if (n == 0) return GSH_OK;
-        GSH_HIP(hipSetDevice(s->device));
-        if (item_type == GSH_ITEM_GR_COMPLEX && !inverted_spectrum && stream_direct_dma())
-            {
-                // items that are the ring's own format: the DMA's destination is the ring (profiles/ab/r03/dropin_direct_dma.txt)
-                int rc = write_items(s, items, n, item_type, 0, s->stream, true, nullptr);
-                if (rc != GSH_OK) return rc;
-                rc = record_push(s, s->next + n, s->stream);
-                if (rc != GSH_OK) return rc;
-                s->next += n;
-                return GSH_OK;
-            }
-        const int slot = s->stage_next;
-        s->stage_next = (s->stage_next + 1) % gsh_stream::NSTAGE;
-        const size_t bytes = static_cast<size_t>(n) * isz;
-        if (s->stage_done[slot] == nullptr)
-            GSH_HIP(hipEventCreateWithFlags(&s->stage_done[slot], hipEventDisableTiming));
-        else
-            GSH_HIP(hipEventSynchronize(s->stage_done[slot]));  // the conversion that read this device buffer four pushes ago
-        if (bytes > s->stage_cap[slot])
-            {
-                if (s->h_stage[slot]) GSH_HIP(release_buffer(s, s->h_stage[slot], true));
-                if (s->d_stage[slot]) GSH_HIP(release_buffer(s, s->d_stage[slot], false));
-                s->h_stage[slot] = nullptr;
-                s->d_stage[slot] = nullptr;
-                s->stage_cap[slot] = 0;
-                const size_t cap = bytes + bytes / 2;
-                GSH_HIP(hipHostMalloc(&s->h_stage[slot], cap, hipHostMallocDefault));  // (kept in step with the staged path, which shares the slots)
-                GSH_HIP(hipMalloc(&s->d_stage[slot], cap));
-                s->stage_cap[slot] = cap;
-            }
+        int rc = check_item_push(s, items, n, item_type);
+        if (rc != GSH_OK) return rc;
+        if (!open_push(s, n, first_index, &rc)) return rc;
+        if (direct_dma(item_type, inverted_spectrum)) return write_and_commit(s, items, n, item_type, 0, s->stream, true);  // (takes no staging slot)
+        const size_t bytes = static_cast<size_t>(n) * gsh::item_bytes(item_type);
+        int slot = 0;
+        rc = stage_slot(s, bytes, &slot);
+        if (rc != GSH_OK) return rc;
         GSH_HIP(hipMemcpyAsync(s->d_stage[slot], items, bytes, hipMemcpyHostToDevice, s->stream));
-        int rc = write_items(s, s->d_stage[slot], n, item_type, inverted_spectrum ? 1 : 0, s->stream);
+        rc = write_items(s, s->d_stage[slot], n, item_type, inverted_spectrum ? 1 : 0, s->stream);
         if (rc != GSH_OK) return rc;
-        GSH_HIP(hipEventRecord(s->stage_done[slot], s->stream));
-        rc = record_push(s, s->next + n, s->stream);
-        if (rc != GSH_OK) return rc;
-        s->next += n;
-        return GSH_OK;
+        return commit_staged(s, slot, n);
     }
 
     int gsh_stream_push_packed(gsh_stream_t* s, const gsh_packed_format* fmt, const void* bytes, uint64_t n, int inverted_spectrum, uint64_t* first_index)
     {
         // gsh_stream_push for packed complex samples: the packed bytes cross PCIe into the raw staging buffer, the unpack writes the ring
-        GSH_REQUIRE(s != nullptr, "null stream");
-        GSH_REQUIRE(n == 0 || bytes != nullptr, "null items");
         gsh::PackedCode c;
         unsigned long long nbytes = 0;
-        int rc = gsh::packed_ring_format(fmt, n, &c, &nbytes);
+        int rc = check_packed_push(s, fmt, bytes, n, &c, &nbytes);
         if (rc != GSH_OK) return rc;
-        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
-        if (first_index) *first_index = s->next;
-        if (n == 0) return GSH_OK;
-        GSH_HIP(hipSetDevice(s->device));
-        if (nbytes > s->raw_cap)
-            {
-                if (s->d_raw) GSH_HIP(release_buffer(s, s->d_raw, false));
-                s->d_raw = nullptr;
-                s->raw_cap = 0;
-                GSH_HIP(hipMalloc(&s->d_raw, nbytes));
-                s->raw_cap = nbytes;
-            }
+        if (!open_push(s, n, first_index, &rc)) return rc;
+        rc = gsh::stream_raw_staging(s, nbytes);
+        if (rc != GSH_OK) return rc;
         GSH_HIP(hipMemcpyAsync(s->d_raw, bytes, nbytes, hipMemcpyHostToDevice, s->stream));
-        rc = write_items(s, s->d_raw, n, GSH_ITEM_BYTE, inverted_spectrum ? 1 : 0, s->stream, false, nullptr, &c);
+        rc = write_items(s, s->d_raw, n, GSH_ITEM_BYTE, inverted_spectrum ? 1 : 0, s->stream, false, &c);
         if (rc != GSH_OK) return rc;
-        rc = record_push(s, s->next + n, s->stream);
-        if (rc != GSH_OK) return rc;
-        GSH_HIP(hipStreamSynchronize(s->stream));
-        s->next += n;
-        return GSH_OK;
+        return commit_push(s, n, s->stream, true);
     }
 
     int gsh_stream_push_packed_device(gsh_stream_t* s, const gsh_packed_format* fmt, const void* device_bytes, uint64_t n, int inverted_spectrum, void* hip_stream,
         uint64_t* first_index)
     {
-        GSH_REQUIRE(s != nullptr, "null stream");
-        GSH_REQUIRE(n == 0 || device_bytes != nullptr, "null items");
         gsh::PackedCode c;
         unsigned long long nbytes = 0;
-        int rc = gsh::packed_ring_format(fmt, n, &c, &nbytes);
+        int rc = check_packed_push(s, fmt, device_bytes, n, &c, &nbytes);
         if (rc != GSH_OK) return rc;
-        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
         GSH_REQUIRE(reinterpret_cast<uintptr_t>(device_bytes) % gsh::packed_alignment(c) == 0, "device_bytes: the registers of packed family %d must be %zu-byte aligned",
             fmt->family, gsh::packed_alignment(c));
-        if (first_index) *first_index = s->next;
-        if (n == 0) return GSH_OK;
-        GSH_HIP(hipSetDevice(s->device));
+        if (!open_push(s, n, first_index, &rc)) return rc;
         hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
         rc = gsh::stream_write_device_packed(s, device_bytes, c, n, inverted_spectrum ? 1 : 0, st);
         if (rc != GSH_OK) return rc;
@@ -811,27 +765,18 @@ extern "C"
         uint64_t* first_index)
     {
         // gsh_stream_push_pinned_async for packed complex samples: page-locked packed bytes -> device staging (DMA) -> unpack into the ring; nothing waits here
-        GSH_REQUIRE(s != nullptr, "null stream");
-        GSH_REQUIRE(n == 0 || bytes != nullptr, "null items");
         gsh::PackedCode c;
         unsigned long long nbytes = 0;
-        int rc = gsh::packed_ring_format(fmt, n, &c, &nbytes);
+        int rc = check_packed_push(s, fmt, bytes, n, &c, &nbytes);
         if (rc != GSH_OK) return rc;
-        GSH_REQUIRE(n <= s->capacity, "a push of %llu samples exceeds the ring capacity %llu", static_cast<unsigned long long>(n), s->capacity);
-        if (first_index) *first_index = s->next;
-        if (n == 0) return GSH_OK;
-        GSH_HIP(hipSetDevice(s->device));
+        if (!open_push(s, n, first_index, &rc)) return rc;
         int slot = 0;
-        rc = packed_stage_slot(s, nbytes, &slot);
+        rc = stage_slot(s, nbytes, &slot);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipMemcpyAsync(s->d_stage[slot], bytes, nbytes, hipMemcpyHostToDevice, s->stream));
-        rc = write_items(s, s->d_stage[slot], n, GSH_ITEM_BYTE, inverted_spectrum ? 1 : 0, s->stream, false, nullptr, &c);
+        rc = write_items(s, s->d_stage[slot], n, GSH_ITEM_BYTE, inverted_spectrum ? 1 : 0, s->stream, false, &c);
         if (rc != GSH_OK) return rc;
-        GSH_HIP(hipEventRecord(s->stage_done[slot], s->stream));
-        rc = record_push(s, s->next + n, s->stream);
-        if (rc != GSH_OK) return rc;
-        s->next += n;
-        return GSH_OK;
+        return commit_staged(s, slot, n);
     }
 
     int gsh_stream_push_packed_multi(gsh_stream_t* const* rings, const int32_t* channels, int n_rings, const gsh_packed_format* fmt, const void* bytes,
@@ -896,7 +841,7 @@ extern "C"
         gsh_stream* s = rings[0];
         GSH_HIP(hipSetDevice(s->device));
         int slot = 0;
-        rc = packed_stage_slot(s, nbytes, &slot);
+        rc = stage_slot(s, nbytes, &slot);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipMemcpyAsync(s->d_stage[slot], bytes, nbytes, hipMemcpyHostToDevice, s->stream));
         rc = gsh::stream_write_device_packed_multi(rings, ch, n_rings, s->d_stage[slot], c, n, inverted_spectrum ? 1 : 0, s->stream);

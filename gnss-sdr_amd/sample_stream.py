@@ -427,6 +427,27 @@ class SampleStream:
         check(self._lib.gsh_stream_push_async(self._h, C.c_void_p(ptr), n, ITEM_TYPES[item_type], int(inverted_spectrum), C.byref(first)))
         return int(first.value)
 
+    def push_staged(self, items: np.ndarray, item_type: str = "gr_complex", inverted_spectrum: bool = False) -> int:
+        """gsh_stream_push_staged: `items` (any host memory) is copied into the ring's page-locked staging on the spot, so the array is free on
+        return; the DMA and the conversion are queued, nothing waits but for the push that used the staging pair four pushes ago."""
+        t = ITEM_TYPES[item_type]
+        a = np.ascontiguousarray(items, _NP[t])
+        n = a.size if t == GSH_ITEM_GR_COMPLEX else a.size // 2
+        first = C.c_uint64(0)
+        check(self._lib.gsh_stream_push_staged(self._h, C.c_void_p(a.ctypes.data) if n else None, n, t, int(inverted_spectrum), C.byref(first)))
+        return int(first.value)
+
+    def push_pinned_async(self, items: np.ndarray, item_type: str = "gr_complex", inverted_spectrum: bool = False) -> int:
+        """gsh_stream_push_pinned_async: `items` lies in page-locked memory (gsh_host_register) and must stay untouched until wait_copied() /
+        wait_copied_upto() covers the push; the DMA and the conversion are queued, nothing waits."""
+        t = ITEM_TYPES[item_type]
+        a = np.ascontiguousarray(items, _NP[t])
+        n = a.size if t == GSH_ITEM_GR_COMPLEX else a.size // 2
+        self._keep_async = getattr(self, "_keep_async", [])[-3:] + [a]
+        first = C.c_uint64(0)
+        check(self._lib.gsh_stream_push_pinned_async(self._h, C.c_void_p(a.ctypes.data) if n else None, n, t, int(inverted_spectrum), C.byref(first)))
+        return int(first.value)
+
     def push_pinned(self, items: np.ndarray, item_type: str = "gr_complex", inverted_spectrum: bool = False) -> int:
         """gsh_stream_push_pinned: `items` is page-locked for the call (gsh_host_register on its pages) and handed to the DMA engine as it lies --
         gr_complex items straight into their ring positions; returns when the array may be reused."""
