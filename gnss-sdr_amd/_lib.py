@@ -160,6 +160,32 @@ class PackedFormat(C.Structure):
     ]
 
 
+class IonChunk(C.Structure):
+    """gsh_ion_chunk (24 bytes): one chunk of an ION_GSMS cycle (ion_gsms.IonLayout builds it)."""
+    _fields_ = [
+        ("size_word", C.c_int32),
+        ("count_words", C.c_int32),
+        ("big_endian", C.c_int32),
+        ("shift", C.c_int32),
+        ("padding", C.c_int32),
+        ("n_streams", C.c_int32),
+    ]
+
+
+class IonStream(C.Structure):
+    """gsh_ion_stream (32 bytes): one stream of an ION_GSMS chunk."""
+    _fields_ = [
+        ("packed_bits", C.c_int32),
+        ("rate_factor", C.c_int32),
+        ("quantization", C.c_int32),
+        ("encoding", C.c_int32),
+        ("format", C.c_int32),
+        ("alignment", C.c_int32),
+        ("lump_shift", C.c_int32),
+        ("negate", C.c_int32),
+    ]
+
+
 class ArrayFormat(C.Structure):
     """gsh_array_format (16 bytes): the item type and layout of an antenna array's streams (array.ArrayFormat builds it)."""
     _fields_ = [
@@ -373,6 +399,16 @@ SYMBOLS = {
                                                             C.POINTER(C.c_uint64)]),
     "gsh_stream_group_push_packed": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     "gsh_stream_group_push_packed_device": (C.c_int, [_P, C.POINTER(PackedFormat), _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "gsh_ion_layout_create": (C.c_int, [C.POINTER(IonChunk), C.c_int, C.POINTER(IonStream), C.c_int, C.POINTER(_P)]),
+    "gsh_ion_layout_destroy": (None, [_P]),
+    "gsh_ion_layout_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "gsh_ion_stream_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gsh_ion_bytes": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gsh_ion_decode_host": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_uint64, _F]),
+    "gsh_ion_unpack_device": (C.c_int, [C.c_int, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(_P), _P]),
+    "gsh_stream_push_ion": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_int32), C.c_int, _P, _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "gsh_stream_push_ion_device": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_int32), C.c_int, _P, _P, C.c_uint64, C.c_int, _P, C.POINTER(C.c_uint64)]),
+    "gsh_stream_push_ion_pinned_async": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_int32), C.c_int, _P, _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     "gsh_beam_create": (C.c_int, [C.c_int, C.POINTER(ArrayFormat), C.c_int, C.POINTER(_P)]),
     "gsh_beam_destroy": (None, [_P]),
     "gsh_beam_set_weights": (C.c_int, [_P, _F]),

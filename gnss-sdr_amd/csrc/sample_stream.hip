@@ -12,6 +12,7 @@
 // so within a push its stream sees copies and conversion, mirror copy, the staging slot's event, the push event, publish_live_kernel, in that order, and
 // the host advances `next` last.  The multi-ring pushes have their own frame, stream_write_device_multi, which orders the rings' streams as well.
 #include "sample_stream.h"
+#include "ion_layout.h"
 #include "packed_unpack.h"
 #include "sample_convert.h"
 #include <algorithm>
@@ -505,6 +506,45 @@ int packed_multi_args(gsh_stream_t* const* rings, const int32_t* channels, int n
     if (rc != GSH_OK) return rc;
     return gsh::stream_multi_check_live(rings, n_rings, n);
 }
+
+// the arguments of a multi-ring ION_GSMS push, all or nothing: the selection, whole cycles, the rings, the live channels; *nbytes = the size of the block
+int ion_push_args(gsh_stream_t* const* rings, const int32_t* streams, int n_rings, const gsh_ion_layout_t* layout, const void* bytes, unsigned long long n,
+    unsigned long long* nbytes)
+{
+    GSH_REQUIRE(rings != nullptr && streams != nullptr && layout != nullptr, "null argument");
+    int cplx = 0, rate = 0;
+    int rc = gsh::ion_check_streams(layout, streams, n_rings, &cplx, &rate);
+    if (rc != GSH_OK) return rc;
+    GSH_REQUIRE(cplx, "stream %d carries real IF samples: they reach a ring through gsh_ion_unpack_device and a FIR (gsh_fir_process_device)", streams[0]);
+    GSH_REQUIRE(n % static_cast<unsigned long long>(rate) == 0, "%llu samples is not a whole number of cycles of %d samples per stream", n, rate);
+    GSH_REQUIRE(n == 0 || bytes != nullptr, "null items");
+    *nbytes = n / static_cast<unsigned long long>(rate) * layout->l.cycle_bytes;
+    rc = gsh::stream_multi_check_rings(rings, n_rings, n);
+    if (rc != GSH_OK) return rc;
+    return gsh::stream_multi_check_live(rings, n_rings, n);
+}
+
+// the block at d_src, already on the device, into the rings on st: the multi-ring frame around the table-driven unpack
+int ion_write_device(gsh_stream_t* const* rings, const int32_t* streams, int n_rings, const gsh_ion_layout_t* layout, const void* d_src, unsigned long long n,
+    int conj, hipStream_t st)
+{
+    struct Fanout
+    {
+        const gsh_ion_layout_t* layout;
+        const void* d_src;
+        const int32_t* streams;
+        int n_rings, conj;
+    } f{layout, d_src, streams, n_rings, conj};
+    return gsh::stream_write_device_multi(
+        rings, n_rings, n, st,
+        [](void* ctx, unsigned long long first, unsigned long long len, float2* const* dst, hipStream_t s) {
+            const Fanout* f = static_cast<const Fanout*>(ctx);
+            void* d[8];
+            for (int i = 0; i < f->n_rings; i++) d[i] = dst[i];
+            return gsh::ion_unpack(f->layout, f->d_src, first, len, f->conj, f->streams, f->n_rings, d, s);
+        },
+        &f);
+}
 }  // namespace
 
 extern "C"
@@ -845,6 +885,69 @@ extern "C"
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipMemcpyAsync(s->d_stage[slot], bytes, nbytes, hipMemcpyHostToDevice, s->stream));
         rc = gsh::stream_write_device_packed_multi(rings, ch, n_rings, s->d_stage[slot], c, n, inverted_spectrum ? 1 : 0, s->stream);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipEventRecord(s->stage_done[slot], s->stream));
+        return GSH_OK;
+    }
+
+    int gsh_stream_push_ion(gsh_stream_t* const* rings, const int32_t* streams, int n_rings, const gsh_ion_layout_t* layout, const void* bytes,
+        uint64_t n, int inverted_spectrum, uint64_t* first_index)
+    {
+        // gsh_stream_push_packed_multi for an ION_GSMS layout: the block crosses PCIe once into the first ring's raw staging buffer, one pass writes every ring
+        unsigned long long nbytes = 0;
+        int rc = ion_push_args(rings, streams, n_rings, layout, bytes, n, &nbytes);
+        if (rc != GSH_OK) return rc;
+        if (first_index)
+            for (int i = 0; i < n_rings; i++) first_index[i] = rings[i]->next;
+        if (n == 0) return GSH_OK;
+        gsh_stream* s = rings[0];
+        GSH_HIP(hipSetDevice(s->device));
+        rc = gsh::stream_raw_staging(s, nbytes);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipMemcpyAsync(s->d_raw, bytes, nbytes, hipMemcpyHostToDevice, s->stream));
+        rc = ion_write_device(rings, streams, n_rings, layout, s->d_raw, n, inverted_spectrum ? 1 : 0, s->stream);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipStreamSynchronize(s->stream));
+        return GSH_OK;
+    }
+
+    int gsh_stream_push_ion_device(gsh_stream_t* const* rings, const int32_t* streams, int n_rings, const gsh_ion_layout_t* layout,
+        const void* device_bytes, uint64_t n, int inverted_spectrum, void* hip_stream, uint64_t* first_index)
+    {
+        unsigned long long nbytes = 0;
+        int rc = ion_push_args(rings, streams, n_rings, layout, device_bytes, n, &nbytes);
+        if (rc != GSH_OK) return rc;
+        GSH_REQUIRE(reinterpret_cast<uintptr_t>(device_bytes) % layout->l.align == 0, "device_bytes: the %u-byte words of the layout must be %u-byte aligned",
+            layout->l.align, layout->l.align);
+        if (first_index)
+            for (int i = 0; i < n_rings; i++) first_index[i] = rings[i]->next;
+        if (n == 0) return GSH_OK;
+        GSH_HIP(hipSetDevice(rings[0]->device));
+        hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : rings[0]->stream;
+        rc = ion_write_device(rings, streams, n_rings, layout, device_bytes, n, inverted_spectrum ? 1 : 0, st);
+        if (rc != GSH_OK) return rc;
+        if (!hip_stream) GSH_HIP(hipStreamSynchronize(st));
+        return GSH_OK;
+    }
+
+    int gsh_stream_push_ion_pinned_async(gsh_stream_t* const* rings, const int32_t* streams, int n_rings, const gsh_ion_layout_t* layout,
+        const void* bytes, uint64_t n, int inverted_spectrum, uint64_t* first_index)
+    {
+        // page-locked bytes -> one of the first ring's device staging buffers (one DMA) -> one pass into every ring; nothing waits here.  Each ring's
+        // push event is recorded behind that pass, so gsh_stream_wait_copied / _upto on any of the rings covers the DMA out of `bytes`.
+        unsigned long long nbytes = 0;
+        int rc = ion_push_args(rings, streams, n_rings, layout, bytes, n, &nbytes);
+        if (rc != GSH_OK) return rc;
+        if (first_index)
+            for (int i = 0; i < n_rings; i++) first_index[i] = rings[i]->next;
+        if (n == 0) return GSH_OK;
+        gsh_stream* s = rings[0];
+        GSH_HIP(hipSetDevice(s->device));
+        int slot = 0;
+        rc = stage_slot(s, nbytes, &slot);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipMemcpyAsync(s->d_stage[slot], bytes, nbytes, hipMemcpyHostToDevice, s->stream));
+        rc = ion_write_device(rings, streams, n_rings, layout, s->d_stage[slot], n, inverted_spectrum ? 1 : 0, s->stream);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipEventRecord(s->stage_done[slot], s->stream));
         return GSH_OK;

@@ -531,6 +531,105 @@ extern "C"
         uint64_t* first_index);
     int gsh_stream_group_push_packed_device(gsh_stream_group_t* g, const gsh_packed_format* fmt, const void* device_bytes, uint64_t n_samples,
         int inverted_spectrum, uint64_t* first_index);
+    /* ---- ION GNSS SDR metadata standard (ION_GSMS) recordings: the device half of ION_GSMS_Signal_Source (adapters/ion_gsms_signal_source.cc,
+     * gnuradio_blocks/ion_gsms.cc, libs/ion_gsms_chunk_data.{h,cc}, libs/ion_gsms_chunk_unpacking_ctx.h, libs/ion_gsms_stream_encodings.h; "libs/" below).
+     * The general layout of which the GSH_PACKED_* families are special cases; it does not fit gsh_packed_format, so it has a layout object of its own.
+     * BIT STREAM.  A block of a recording is a run of chunk CYCLES; one cycle is the chunks in order, cycle_bytes = sum of size_word x count_words
+     * (<= GSH_ION_MAX_CYCLE_BYTES).  Within one chunk the words in ascending order, each from its most significant bit down, form one bit stream (chunk
+     * shift Left, libs/ion_gsms_chunk_unpacking_ctx.h:46-49,86-89).  A word is little-endian in memory unless big_endian: stream byte b of a little-endian
+     * chunk of W-byte words is memory byte (b / W) W + W - 1 - b % W.  Head padding is skipped first (libs/ion_gsms_chunk_data.cc:149-153), pad = 8 x
+     * size_word x count_words - sum of packed_bits >= 0; then the streams of the chunk in order, packed_bits each, selected or not (:156-167).
+     * A stream's packed_bits are rate_factor samples (:58-59,179-180), each one FIELD when real and two when complex, in the order of `format`; a field
+     * is w = packed_bits / rate_factor bits, halved when complex (:60-65,182-187); the divisions must be exact and 1 <= quantization <= w <= 16.  With
+     * alignment 0 the code is the whole field (q = w); with alignment 1 / 2 it is the top / low q = quantization bits and the rest is ignored.  A
+     * field may straddle words.  Sample k of a stream lies in cycle k / rate_factor.
+     * VALUES.  The code c has q bits, most significant first; g is the Gray-decoded c (g = c ^ c>>1 ^ c>>2 ...):
+     *   OB c - 2^(q-1)      OBA 2c - (2^q - 1)      TC c, or c - 2^q when its top bit is set      TCA 2 TC + 1
+     *   SM sign = top bit, m = the rest: +-m      SMA +-(2m + 1)      MS sign = low bit, m = c >> 1: +-m      MSA +-(2m + 1)
+     *   OG OB(g)      OGA OBA(g)      SIGN (q = 1): 0 -> +1, 1 -> -1
+     * These equal the reference's tables at 2..5 bits (libs/ion_gsms_stream_encodings.h:105-163) for every encoding but MS at 3, 4 and 5 bits (below).
+     * Outputs are float32 and exact: `negate` is applied to the integer value (a zero stays +0), then the conjugation of inverted_spectrum.
+     * DEVIATIONS: the definition is the layout as the reference's code plainly intends it, not the reference as compiled --
+     *   - its word type is signed: a field whose leading bit is set is extracted with an arithmetic shift and then indexes the look-up tables below
+     *     their start (libs/ion_gsms_chunk_unpacking_ctx.h:164-168, libs/ion_gsms_chunk_data.cc:252-266); here fields are unsigned;
+     *   - its masks are `1 << n` computed in int, also for 64-bit words (ctx.h:149,166); here no shift count reaches the operand's width;
+     *   - a field that straddles words is not assembled there (ctx.h:143-161 ORs its two parts into the output at the wrong positions: 12-bit TC
+     *     across 8-bit words AB CD EF gives (-1, -1)); here it is one bit string, (-1348, -529);
+     *   - endianness is a TODO there (chunk_data.cc:141: the host's, little-endian); big_endian is honoured here;
+     *   - the MS tables at 3, 4 and 5 bits repeat the 2-bit row (stream_encodings.h:125,140,155); here MS is regular, as the neighbouring MSA tables are;
+     *   - SIGN passes the raw bit through there (chunk_data.cc:266-269); here it follows the sign convention of SM: 0 -> +1, 1 -> -1;
+     *   - fields of 6 bits and more are passed through undecoded there (:266-269); here every encoding is defined at every width.
+     * NOT BUILT: chunk shift Right (starts one word past the buffer there, ctx.h:50-57) and lump shift Right (writes items count .. 1 there,
+     * chunk_data.cc:219-230): GSH_ERR_UNSUPPORTED; encoding FP: GSH_ERR_UNSUPPORTED; fields over 16 bits; streams of unequal rate in one call. */
+#define GSH_ION_MAX_CHUNKS 16
+#define GSH_ION_MAX_STREAMS 64     /* described per chunk cycle */
+#define GSH_ION_MAX_SELECTED 8     /* per call, as the multi-ring frame */
+#define GSH_ION_MAX_CYCLE_BYTES 4096
+/* encodings, the reference's numbering (libs/ion_gsms_stream_encodings.h:37-48) */
+#define GSH_ION_SIGN 0
+#define GSH_ION_OB 1
+#define GSH_ION_SM 2
+#define GSH_ION_MS 3
+#define GSH_ION_TC 4
+#define GSH_ION_OG 5
+#define GSH_ION_OBA 6
+#define GSH_ION_SMA 7
+#define GSH_ION_MSA 8
+#define GSH_ION_TCA 9
+#define GSH_ION_OGA 10
+#define GSH_ION_FP 11 /* GSH_ERR_UNSUPPORTED */
+    typedef struct
+    {
+        int32_t size_word;   /* 1, 2, 4, 8 bytes */
+        int32_t count_words; /* >= 1 */
+        int32_t big_endian;  /* 0: little-endian words */
+        int32_t shift;       /* 0 Left; 1 Right -> GSH_ERR_UNSUPPORTED */
+        int32_t padding;     /* 0 none / tail, 1 head */
+        int32_t n_streams;   /* streams of this chunk, lumps flattened in file order */
+    } gsh_ion_chunk;
+    typedef struct
+    {
+        int32_t packed_bits, rate_factor, quantization, encoding;
+        int32_t format;     /* GSH_PACKED_REAL / _IQ / _QI */
+        int32_t alignment;  /* 0 undefined: the code is the whole field; 1 left: its top `quantization` bits; 2 right: its low bits */
+        int32_t lump_shift; /* 0 Left / undefined; 1 Right -> GSH_ERR_UNSUPPORTED */
+        int32_t negate;     /* bit 0: negate I (or the real value), bit 1: negate Q */
+    } gsh_ion_stream;
+    typedef struct gsh_ion_layout gsh_ion_layout_t;
+    /* `streams` lists the streams of every chunk in order: chunks[0].n_streams of them, then chunks[1].n_streams ...; n_streams is their total.
+     * GSH_ERR_INVALID for a descriptor that breaks a rule or a limit above, GSH_ERR_UNSUPPORTED for a Right shift or FP.  No GPU. */
+    int gsh_ion_layout_create(const gsh_ion_chunk* chunks, int n_chunks, const gsh_ion_stream* streams, int n_streams, gsh_ion_layout_t** out);
+    void gsh_ion_layout_destroy(gsh_ion_layout_t* layout);
+    int gsh_ion_layout_info(const gsh_ion_layout_t* layout, uint32_t* cycle_bytes, int32_t* n_streams);
+    /* samples of `stream` per cycle (rate_factor), whether it is complex, and the bits of one field (w) */
+    int gsh_ion_stream_info(const gsh_ion_layout_t* layout, int stream, int32_t* samples_per_cycle, int32_t* is_complex, int32_t* field_bits);
+    /* the bytes of the cycles that samples [0, n_samples) of `stream` touch */
+    int gsh_ion_bytes(const gsh_ion_layout_t* layout, int stream, uint64_t n_samples, uint64_t* bytes);
+    /* the host build of the decoder the kernel shares (csrc/ion_gsms.h): samples [first_sample, first_sample + n_samples) of `stream` in the block
+     * `bytes` (host memory, cycle 0 at its first byte) -> out: one float per sample for a real stream, two (I, Q) for a complex one.  No GPU. */
+    int gsh_ion_decode_host(const gsh_ion_layout_t* layout, int stream, const void* bytes, uint64_t first_sample, uint64_t n_samples, float* out);
+    /* one pass over the device-resident block d_src (the start of a cycle, aligned to the largest size_word of the layout) writes samples
+     * [first_sample, first_sample + n_samples) of streams[i] to d_dst[i], i < n_streams <= GSH_ION_MAX_SELECTED: complex64 (8-byte aligned, conjugated
+     * when inverted_spectrum) when the streams are complex, float32 (4-byte aligned; inverted_spectrum must be 0) when they are real.  The streams of
+     * one call have equal samples per cycle and are all complex or all real (GSH_ERR_INVALID otherwise, as the equal slots of LS4); none is named
+     * twice.  first_sample may fall inside a cycle and n_samples need not end at one.  Real streams are IF samples: they reach a ring through
+     * gsh_fir_process_device with the floats of this call.  Asynchronous on hip_stream. */
+    int gsh_ion_unpack_device(int device, const gsh_ion_layout_t* layout, const void* d_src, uint64_t first_sample, uint64_t n_samples,
+        int inverted_spectrum, const int32_t* streams, int n_streams, void* const* d_dst, void* hip_stream);
+    /* One push of a block of whole cycles into n_rings rings: complex stream streams[i] goes to rings[i].  The block crosses PCIe once and one pass
+     * over it writes every ring; afterwards each ring is, bit for bit and index for index, what gsh_stream_push of the host-decoded samples
+     * (gsh_ion_decode_host, gr_complex, the same inverted_spectrum) would have left, and gsh_stream_wait / _wait_copied / _wait_copied_upto work on
+     * every ring of the call.  n_samples counts samples per stream and must be whole cycles.  first_index: n_rings entries, or NULL.  All or nothing,
+     * as gsh_stream_push_packed_multi: GSH_ERR_INVALID for a real stream, streams of unequal rate, a stream or ring named twice, a partial cycle,
+     * rings on different devices, a push above a capacity; GSH_ERR_STATE for a live tracking channel whose samples the push would overwrite; then
+     * no ring advances.  The device form takes a block aligned to the largest size_word and works on hip_stream (NULL: the first ring's own
+     * stream, synchronous). */
+    int gsh_stream_push_ion(gsh_stream_t* const* rings, const int32_t* streams, int n_rings, const gsh_ion_layout_t* layout, const void* bytes,
+        uint64_t n_samples, int inverted_spectrum, uint64_t* first_index);
+    int gsh_stream_push_ion_device(gsh_stream_t* const* rings, const int32_t* streams, int n_rings, const gsh_ion_layout_t* layout,
+        const void* device_bytes, uint64_t n_samples, int inverted_spectrum, void* hip_stream, uint64_t* first_index);
+    int gsh_stream_push_ion_pinned_async(gsh_stream_t* const* rings, const int32_t* streams, int n_rings, const gsh_ion_layout_t* layout,
+        const void* bytes, uint64_t n_samples, int inverted_spectrum, uint64_t* first_index);
     /* ---- antenna array front end: the spatial filter of Array_Signal_Conditioner (Beamformer_Filter, gnss_block_factory.cc:819-839;
      * src/algorithms/input_filter/gnuradio_blocks/beamformer.{h,cc}) for up to 8 antennas, several beams at once, each beam straight into its own
      * ring, and the array covariance the weights are computed from.
