@@ -164,16 +164,31 @@ class PcpsAcquisitionBank:
         check(self._lib.gsh_acq_dwell_cshort(self._h, x16.ctypes.data_as(C.POINTER(C.c_int16)), n_prn, int(accumulate), dwell_count, res))
         return [self._to_dict(r) for r in res]
 
-    def dwell_step2(self, x: np.ndarray, prn_slots, doppler_centers, input_powers=None, accumulate: bool = False, dwell_count: int = 1):
-        """Step two of make_two_steps (acq.cc:294-301, 428-437, 605-624): a narrow grid around each slot's step-one Doppler."""
+    def dwell_slots(self, x: np.ndarray, prn_slots):
+        """One acquisition_core pass over x[:consumed_samples] for the listed prn slots, in the order listed (gsh_acq_dwell_slots)."""
         x = np.ascontiguousarray(x, np.complex64)
+        if len(x) < self.conf.consumed_samples:
+            raise ValueError("input shorter than consumed_samples")
+        slots = np.ascontiguousarray(prn_slots, np.uint32)
+        res = (AcqResult * len(slots))()
+        check(self._lib.gsh_acq_dwell_slots(self._h, fptr(x), len(slots), slots.ctypes.data_as(C.POINTER(C.c_uint32)), res))
+        return [self._to_dict(r) for r in res]
+
+    def dwell_step2(self, x, prn_slots, doppler_centers, input_powers=None, accumulate: bool = False, dwell_count: int = 1):
+        """Step two of make_two_steps (acq.cc:294-301, 428-437, 605-624): a narrow grid around each slot's step-one Doppler.
+        x: numpy array or torch cuda tensor."""
         n = len(prn_slots)
         slots = np.ascontiguousarray(prn_slots, np.uint32)
         cen = np.ascontiguousarray(doppler_centers, np.float32)
         pw = np.ascontiguousarray(input_powers if input_powers is not None else np.zeros(n), np.float32)
         res = (AcqResult * n)()
-        check(self._lib.gsh_acq_dwell_step2(self._h, fptr(x), n, slots.ctypes.data_as(C.POINTER(C.c_uint32)), fptr(cen),
-                                            fptr(pw) if (input_powers is not None or self.conf.use_cfar) else None, int(accumulate), dwell_count, res))
+        tail = (n, slots.ctypes.data_as(C.POINTER(C.c_uint32)), fptr(cen),
+                fptr(pw) if (input_powers is not None or self.conf.use_cfar) else None, int(accumulate), dwell_count, res)
+        if hasattr(x, "data_ptr"):
+            check(self._lib.gsh_acq_dwell_step2_device(self._h, C.c_void_p(x.data_ptr()), *tail))
+        else:
+            x = np.ascontiguousarray(x, np.complex64)
+            check(self._lib.gsh_acq_dwell_step2(self._h, fptr(x), *tail))
         return [self._to_dict(r) for r in res]
 
     def dwell_ring(self, ring, first_sample: int, n_prn: int, accumulate: bool = False, dwell_count: int = 1):

@@ -3,6 +3,16 @@
 // (gnss-sdr, src/algorithms/acquisition/gnuradio_blocks/pcps_acquisition.cc:648-684) for a whole batch of
 // local codes: the D wiped-off forward FFTs are computed ONCE and shared by every PRN (the reference recomputes
 // them in every channel's block).
+//
+// Every entry that hands a block to the device and runs a batch is a short sequence of the same steps, each written once below:
+//     check_dwell / check_slots            the arguments, in the order their errors are reported
+//     take_host / take_device / take_cshort   the block into d_in: through the pinned stage, device to device, or int16 converted on the device
+//     whole_batch                          the description of one batch (Batch): which code spectra and bins, where its records and grid rows
+//                                          start, on which lane it runs -- here the handle's full batch; the entries change what differs
+//     run_batch                            forward transforms and correlation of one Batch: the on-chip / four-step dispatch, the chunking over
+//                                          PRNs, whether the grid is stored (stores_grid)
+//     fetch_results / to_result            the records back to the host, one gsh_acq_result from one of them
+// The buffers a batch in flight writes form a lane (gsh_acq::Lane); lane 0 is the handle's own set, lane_alloc / lane_free serve every lane.
 #include "pcps_fft.h"
 #include "sample_convert.h"
 #include "sample_stream.h"
@@ -18,7 +28,6 @@ struct gsh_acq
 {
     int device{0};
     gsh_acq_conf conf{};
-    hipStream_t stream{nullptr};
     gsh::FftPlan plan;
     int n_bins{0};
     std::vector<float> h_bins_hz;   // the float the reference hands to update_local_carrier (acq.cc:289, :299)
@@ -28,19 +37,12 @@ struct gsh_acq
     float* d_bins2_hz{nullptr};
     int16_t* d_in16{nullptr};       // cshort input staging (gsh_acq_dwell_cshort), allocated on first use
     float2* d_in{nullptr};        // consumed_samples
-    float2* d_spectra{nullptr};   // n_bins * n
     float2* d_codes{nullptr};     // max_prn * n   (forward FFT of the placed code, permuted layout, unconjugated)
     float2* d_codes_sel{nullptr}; // gsh_acq_dwell_slots: the spectra of the slots of one batch side by side (allocated on first use)
     float2* d_tmp{nullptr};       // chunk_prn * n_bins * n
     float* d_grid{nullptr};       // max_prn * n_bins * effective
-    gsh::RowStat* d_rows{nullptr};
     gsh_acq_pair_peak* d_pair{nullptr};  // gsh_acq_noncoherent_pair_peaks: one record per bin
-    gsh::RowStat* d_subrows{nullptr};  // split plans (N = S * M): the sub-cells' records, S per (PRN, bin)
-    gsh::RowStat* d_waverows{nullptr}; // on-chip path: the cells' per-wave partial records, ONCHIP_MAX_WAVES per (PRN, bin, sub-cell) (pcps_fft.h)
     int split{0};
-    float2* d_z{nullptr};              // decimation-in-time split plans (gsh::onchip_dit): the sub-cells' length-M transforms, max_prn * n_bins * n
-    gsh::DevAcqResult* d_results{nullptr};
-    unsigned* d_arrivals{nullptr};          // on-chip path: per-PRN arrival counters, zero between launches
     gsh::DevAcqResult* h_results{nullptr};  // pinned
     float2* h_stage{nullptr};               // pinned, max(consumed, code length)
     std::vector<char> code_set;
@@ -60,24 +62,26 @@ struct gsh_acq
     uint32_t* d_tc_delays{nullptr};
     float2* d_tc_out{nullptr};
     hipEvent_t ev0{nullptr}, ev1{nullptr};
-    // further issue lanes for gsh_acq_time_dwells_pipelined (on-chip path): a stream and per-batch buffers each, so that batch k+1's forward transforms
-    // and first cells fill the compute units batch k's last cells leave idle (lane 0 is the handle's own stream and buffers)
+    // An issue lane: a stream and the buffers one batch in flight writes.  Lane 0 is the handle's own set (gsh_acq_create), on which every entry runs;
+    // gsh_acq_time_dwells_pipelined (on-chip path) adds further ones, so that batch k+1's forward transforms and first cells fill the compute
+    // units batch k's last cells leave idle.
     struct Lane
     {
         hipStream_t stream{nullptr};
-        float2* d_spectra{nullptr};
+        float2* d_spectra{nullptr};        // n_bins * n
         gsh::RowStat* d_rows{nullptr};
-        gsh::RowStat* d_subrows{nullptr};
-        gsh::RowStat* d_waverows{nullptr};
-        float2* d_z{nullptr};
+        gsh::RowStat* d_subrows{nullptr};  // split plans (N = S * M): the sub-cells' records, S per (PRN, bin)
+        gsh::RowStat* d_waverows{nullptr}; // on-chip path: the cells' per-wave partial records, ONCHIP_MAX_WAVES per (PRN, bin, sub-cell) (pcps_fft.h)
+        float2* d_z{nullptr};              // decimation-in-time split plans (gsh::onchip_dit): the sub-cells' length-M transforms, max_prn * n_bins * n
         gsh::DevAcqResult* d_results{nullptr};
-        unsigned* d_arrivals{nullptr};
+        unsigned* d_arrivals{nullptr};     // on-chip path: per-PRN arrival counters, zero between launches
         hipEvent_t ev{nullptr};
         hipEvent_t ev_cells{nullptr};  // recorded behind the lane's last cell launches (decimation-in-time plans: the next batch's cells wait for it, gsh_acq_time_dwells_pipelined)
     };
     static constexpr int MAX_LANES = 4;
     Lane lane[MAX_LANES];
     int n_lanes{1};
+    hipStream_t stream() const { return lane[0].stream; }
 };
 
 namespace
@@ -188,42 +192,84 @@ void fill_bins(gsh_acq* a)
 
 int upload_bins(gsh_acq* a)
 {
-    GSH_HIP(hipMemcpyAsync(a->d_bins_hz, a->h_bins_hz.data(), sizeof(float) * a->n_bins, hipMemcpyHostToDevice, a->stream));
-    GSH_HIP(hipStreamSynchronize(a->stream));
+    GSH_HIP(hipMemcpyAsync(a->d_bins_hz, a->h_bins_hz.data(), sizeof(float) * a->n_bins, hipMemcpyHostToDevice, a->stream()));
+    GSH_HIP(hipStreamSynchronize(a->stream()));
     return GSH_OK;
 }
 
-// queue one full dwell batch on the handle's stream (input already in d_in)
-int enqueue_dwell(gsh_acq* a, uint32_t n_prn, int accumulate, uint32_t dwell_count)
+// whether a batch writes its |y|^2 into the magnitude grid: always on a handle that keeps one; on a no_grid handle only for the peak-ratio statistic of a
+// split plan, whose second peak is found by scanning the stored winning row (gsh_acq_create)
+bool stores_grid(const gsh_acq* a) { return !a->conf.no_grid || (a->split > 0 && !a->conf.use_cfar); }
+
+// What varies between the batches the entries run; everything else comes from the handle.
+struct Batch
+{
+    const float2* codes;  // n_prn code spectra side by side
+    const float* bins;    // n_bins wipe-off frequencies (device)
+    int n_bins;
+    int n_prn;
+    float* grid;          // the batch's first PRN's rows of the magnitude grid
+    size_t first;         // the batch's first PRN record in the lane's buffers (step two: one batch per listed slot, record i)
+    int accumulate;
+    uint32_t dwell_count;  // 0 counts as 1
+    float weight;
+    int fold;
+    bool store;            // false: several batches are in flight and must not share the magnitude grid
+    const gsh_acq::Lane* lane;
+    hipEvent_t cells_after;  // on-chip path: the cells wait for this event / this event is recorded behind them (nullptr: none)
+    hipEvent_t cells_done;
+};
+
+// the handle's own batch: prn slots 0..n_prn-1 over the wide Doppler grid, on lane 0
+Batch whole_batch(const gsh_acq* a, uint32_t n_prn, int accumulate, uint32_t dwell_count)
+{
+    return Batch{a->d_codes, a->d_bins_hz, a->n_bins, static_cast<int>(n_prn), a->d_grid, 0, accumulate, dwell_count, a->grid_weight,
+        static_cast<int>(std::max(1u, a->conf.fold)), true, &a->lane[0], nullptr, nullptr};
+}
+
+// queue one batch on its lane's stream (input already in d_in)
+int run_batch(gsh_acq* a, const Batch& b)
 {
     const gsh_acq_conf& c = a->conf;
     const int n = static_cast<int>(c.fft_size);
     const int eff = static_cast<int>(c.effective_fft_size);
+    const gsh_acq::Lane& ln = *b.lane;
+    const unsigned dwells = b.dwell_count ? b.dwell_count : 1u;
+    const int lag_off = c.bit_transition_flag ? eff : 0;  // acq.cc:544
+    const size_t cell0 = b.first * b.n_bins;
     if (a->onchip)
         {
             // acq.cc:657-664 (zero padding) + :531-535 (wipe-off, forward FFT): one work-group per bin
-            int rc = gsh::onchip_forward(n, a->d_in, 0, static_cast<int>(c.consumed_samples), 0, a->d_bins_hz, static_cast<double>(c.fs_in),
-                a->d_spectra, a->n_bins, a->stream, static_cast<int>(std::max(1u, c.fold)));
+            int rc = gsh::onchip_forward(n, a->d_in, 0, static_cast<int>(c.consumed_samples), 0, b.bins, static_cast<double>(c.fs_in), ln.d_spectra, b.n_bins,
+                ln.stream, b.fold);
             if (rc != GSH_OK) return rc;
+            if (b.cells_after != nullptr) GSH_HIP(hipStreamWaitEvent(ln.stream, b.cells_after, 0));
             // acq.cc:538-553 + the per-row part of :409-519: one work-group per (PRN, bin) cell, nothing leaves the CU
-            return gsh::onchip_correlate(n, a->d_spectra, a->d_codes, a->d_grid, a->d_rows, a->d_subrows, a->d_results, a->d_arrivals, static_cast<int>(n_prn),
-                a->n_bins, c.bit_transition_flag ? eff : 0, eff, accumulate, (c.no_grid && !(a->split > 0 && !c.use_cfar)) ? 0 : 1, static_cast<int>(c.samples_per_chip), c.use_cfar, dwell_count ? dwell_count : 1u,
-                a->grid_weight, a->stream, a->d_z, a->d_waverows);
+            const size_t sub = static_cast<size_t>(std::max(a->split, 1));
+            rc = gsh::onchip_correlate(n, ln.d_spectra, b.codes, b.grid, ln.d_rows + cell0, ln.d_subrows ? ln.d_subrows + cell0 * a->split : nullptr,
+                ln.d_results + b.first, ln.d_arrivals + b.first, b.n_prn, b.n_bins, lag_off, eff, b.accumulate, (b.store && stores_grid(a)) ? 1 : 0,
+                static_cast<int>(c.samples_per_chip), c.use_cfar, dwells, b.weight, ln.stream, ln.d_z ? ln.d_z + cell0 * n : nullptr,
+                ln.d_waverows + cell0 * sub * gsh::ONCHIP_MAX_WAVES);
+            if (rc != GSH_OK) return rc;
+            if (b.cells_done != nullptr) GSH_HIP(hipEventRecord(b.cells_done, ln.stream));
+            return GSH_OK;
         }
     // acq.cc:657-664 (zero padding) + :531-535 (wipe-off, forward FFT) for every bin
-    int rc = gsh::fft_forward(a->plan, a->d_in, 0, static_cast<int>(c.consumed_samples), 0, a->d_bins_hz, static_cast<double>(c.fs_in),
-        a->d_tmp, a->d_spectra, a->n_bins, a->stream, static_cast<int>(std::max(1u, c.fold)));
+    int rc = gsh::fft_forward(a->plan, a->d_in, 0, static_cast<int>(c.consumed_samples), 0, b.bins, static_cast<double>(c.fs_in), a->d_tmp, ln.d_spectra,
+        b.n_bins, ln.stream, b.fold);
     if (rc != GSH_OK) return rc;
-    const int grid_off = a->padded ? n - eff : (c.bit_transition_flag ? eff : 0);  // acq.cc:544; padded: the lags sit in the last N outputs
-    for (uint32_t p0 = 0; p0 < n_prn; p0 += static_cast<uint32_t>(a->chunk_prn))
+    // padded: the lags sit in the last N outputs and the magnitudes are rescaled.  (Step two never meets a padded handle -- gsh_acq_create refuses the
+    // combination --, so its batches pass here with pad_scale 1.0f and the plain lag offset.)
+    const int grid_off = a->padded ? n - eff : lag_off;
+    for (int p0 = 0; p0 < b.n_prn; p0 += a->chunk_prn)
         {
-            const int np = static_cast<int>(std::min<uint32_t>(a->chunk_prn, n_prn - p0));
-            rc = gsh::correlate_grid(a->plan, a->d_spectra, a->d_codes + static_cast<size_t>(p0) * n, a->d_tmp,
-                a->d_grid + static_cast<size_t>(p0) * a->n_bins * eff, np, a->n_bins, grid_off, eff, accumulate, a->grid_weight * a->pad_scale, a->stream);
+            const int np = std::min(a->chunk_prn, b.n_prn - p0);
+            rc = gsh::correlate_grid(a->plan, ln.d_spectra, b.codes + static_cast<size_t>(p0) * n, a->d_tmp, b.grid + static_cast<size_t>(p0) * a->n_bins * eff, np,
+                b.n_bins, grid_off, eff, b.accumulate, b.weight * a->pad_scale, ln.stream);
             if (rc != GSH_OK) return rc;
         }
-    return gsh::grid_statistics(a->d_grid, a->d_rows, a->d_results, static_cast<int>(n_prn), a->n_bins, eff,
-        static_cast<int>(c.samples_per_chip), c.use_cfar, dwell_count ? dwell_count : 1u, a->stream);
+    return gsh::grid_statistics(b.grid, ln.d_rows + cell0, ln.d_results + b.first, b.n_prn, b.n_bins, eff, static_cast<int>(c.samples_per_chip), c.use_cfar, dwells,
+        ln.stream);
 }
 
 // time-domain correlation of the resident block with an unfolded code at a few candidate delays, at one Doppler bin
@@ -382,15 +428,6 @@ __global__ __launch_bounds__(1024) void pair_peaks_kernel(PairPeakArgs a)
         }
 }
 
-int check_dwell_args(gsh_acq* a, uint32_t n_prn, const void* results)
-{
-    GSH_REQUIRE(a != nullptr && results != nullptr, "null argument");
-    GSH_REQUIRE(n_prn >= 1 && n_prn <= a->conf.max_prn, "n_prn %u outside 1..%u", n_prn, a->conf.max_prn);
-    for (uint32_t p = 0; p < n_prn; p++)
-        if (!a->code_set[p]) return set_error(GSH_ERR_STATE, "local code of prn slot %u has not been set (set_local_code)", p);
-    return GSH_OK;
-}
-
 int check_accumulate(gsh_acq* a, int accumulate)
 {
     if (accumulate && a->conf.no_grid)
@@ -398,23 +435,146 @@ int check_accumulate(gsh_acq* a, int accumulate)
     return GSH_OK;
 }
 
-int finish_results(gsh_acq* a, uint32_t n_prn, gsh_acq_result* results)
+// the arguments of a dwell over prn slots 0..n_prn-1
+int check_dwell(gsh_acq* a, uint32_t n_prn, int accumulate, const void* results)
 {
-    GSH_HIP(hipMemcpyAsync(a->h_results, a->d_results, sizeof(gsh::DevAcqResult) * n_prn, hipMemcpyDeviceToHost, a->stream));
-    GSH_HIP(hipStreamSynchronize(a->stream));
+    GSH_REQUIRE(a != nullptr && results != nullptr, "null argument");
+    GSH_REQUIRE(n_prn >= 1 && n_prn <= a->conf.max_prn, "n_prn %u outside 1..%u", n_prn, a->conf.max_prn);
     for (uint32_t p = 0; p < n_prn; p++)
+        if (!a->code_set[p]) return set_error(GSH_ERR_STATE, "local code of prn slot %u has not been set (set_local_code)", p);
+    return check_accumulate(a, accumulate);
+}
+
+// a list of prn slots: each in range and with its code set.  Step two hands its Doppler centres along: each is then finite, and no slot is listed
+// twice (every listed slot's rows of the one grid are written).
+int check_slots(gsh_acq* a, uint32_t n, const uint32_t* prn_slots, const float* step2_centers)
+{
+    for (uint32_t i = 0; i < n; i++)
         {
-            const gsh::DevAcqResult& r = a->h_results[p];
-            gsh_acq_result& o = results[p];
-            o.index_time = r.index_time;
-            o.index_doppler = r.index_doppler;
-            o.doppler_hz = -a->conf.doppler_max + a->conf.doppler_center + a->conf.doppler_step * static_cast<int32_t>(r.index_doppler);  // acq.cc:431/:478
-            o.acq_delay_samples = std::fmod(static_cast<float>(r.index_time), a->conf.samples_per_code);                                    // acq.cc:582
-            o.peak = r.peak;
-            o.input_power = r.input_power;
-            o.second_peak = r.second_peak;
-            o.test_statistics = r.test_statistics;
+            GSH_REQUIRE(prn_slots[i] < a->conf.max_prn, "prn slot %u outside 0..%u", prn_slots[i], a->conf.max_prn - 1);
+            if (!a->code_set[prn_slots[i]]) return set_error(GSH_ERR_STATE, "local code of prn slot %u has not been set (set_local_code)", prn_slots[i]);
+            if (step2_centers == nullptr) continue;
+            GSH_REQUIRE(std::isfinite(step2_centers[i]), "doppler_center_step_two[%u] is not finite", i);
+            for (uint32_t k = 0; k < i; k++) GSH_REQUIRE(prn_slots[k] != prn_slots[i], "prn slot %u listed twice", prn_slots[i]);
         }
+    return GSH_OK;
+}
+
+// ---- the block into d_in (on the handle's stream; only gsh_acq_stage_input waits for the copy) ----
+int take_host(gsh_acq* a, const float* in_iq)
+{
+    std::memcpy(a->h_stage, in_iq, sizeof(float2) * a->conf.consumed_samples);
+    GSH_HIP(hipMemcpyAsync(a->d_in, a->h_stage, sizeof(float2) * a->conf.consumed_samples, hipMemcpyHostToDevice, a->stream()));
+    a->have_input = true;
+    return GSH_OK;
+}
+
+int take_device(gsh_acq* a, const void* device_in_iq)
+{
+    GSH_HIP(hipMemcpyAsync(a->d_in, device_in_iq, sizeof(float2) * a->conf.consumed_samples, hipMemcpyDeviceToDevice, a->stream()));
+    a->have_input = true;
+    return GSH_OK;
+}
+
+int take_cshort(gsh_acq* a, const int16_t* in_iq16)
+{
+    const size_t n = a->conf.consumed_samples;
+    if (a->d_in16 == nullptr) GSH_HIP(hipMalloc(&a->d_in16, sizeof(int16_t) * 2 * n));
+    // h_stage holds fft_size complex64 = room for 4 * fft_size int16
+    std::memcpy(a->h_stage, in_iq16, sizeof(int16_t) * 2 * n);
+    GSH_HIP(hipMemcpyAsync(a->d_in16, a->h_stage, sizeof(int16_t) * 2 * n, hipMemcpyHostToDevice, a->stream()));
+    const int rc = gsh::convert_to_complex(a->d_in16, GSH_ITEM_SHORT, 0, a->d_in, n, a->stream());  // acq.cc:653-656
+    if (rc != GSH_OK) return rc;
+    a->have_input = true;
+    return GSH_OK;
+}
+
+// ---- results ----
+// the first n records of lane 0 into h_results
+int fetch_results(gsh_acq* a, uint32_t n)
+{
+    GSH_HIP(hipMemcpyAsync(a->h_results, a->lane[0].d_results, sizeof(gsh::DevAcqResult) * n, hipMemcpyDeviceToHost, a->stream()));
+    GSH_HIP(hipStreamSynchronize(a->stream()));
+    return GSH_OK;
+}
+
+void to_result(const gsh_acq_conf& c, const gsh::DevAcqResult& r, int32_t doppler_hz, gsh_acq_result& o)
+{
+    o.index_time = r.index_time;
+    o.index_doppler = r.index_doppler;
+    o.doppler_hz = doppler_hz;
+    o.acq_delay_samples = std::fmod(static_cast<float>(r.index_time), c.samples_per_code);  // acq.cc:582
+    o.peak = r.peak;
+    o.input_power = r.input_power;
+    o.second_peak = r.second_peak;
+    o.test_statistics = r.test_statistics;
+}
+
+// a batch of the wide grid on lane 0, and its results
+int run_dwell(gsh_acq* a, const Batch& b, gsh_acq_result* results)
+{
+    int rc = run_batch(a, b);
+    if (rc == GSH_OK) rc = fetch_results(a, static_cast<uint32_t>(b.n_prn));
+    if (rc != GSH_OK) return rc;
+    const gsh_acq_conf& c = a->conf;
+    for (int p = 0; p < b.n_prn; p++)
+        to_result(c, a->h_results[p], -c.doppler_max + c.doppler_center + c.doppler_step * static_cast<int32_t>(a->h_results[p].index_doppler), results[p]);  // acq.cc:431/:478
+    return GSH_OK;
+}
+
+// ---- lanes ----
+// the buffers of one lane, each only where the slot does not hold one yet: a call that failed part-way -- an allocation refused -- left what it had got
+// in the slot, and the next call must finish that lane, not overwrite its pointers; lane_free frees whatever a slot holds.  cell_bins: the bins per PRN
+// the per-cell buffers are sized for (lane 0 also runs step two's batches, the further lanes only the wide grid).
+int lane_alloc(gsh_acq* a, gsh_acq::Lane& ln, size_t cell_bins)
+{
+    const size_t n = a->conf.fft_size, D = static_cast<size_t>(a->n_bins), P = a->conf.max_prn;
+    const size_t cells = P * cell_bins;
+    if (ln.d_spectra == nullptr) GSH_HIP(hipMalloc(&ln.d_spectra, sizeof(float2) * D * n));
+    if (ln.d_rows == nullptr) GSH_HIP(hipMalloc(&ln.d_rows, sizeof(gsh::RowStat) * P * D));
+    if (a->split > 0 && ln.d_subrows == nullptr) GSH_HIP(hipMalloc(&ln.d_subrows, sizeof(gsh::RowStat) * cells * a->split));
+    if (a->onchip && ln.d_waverows == nullptr)
+        GSH_HIP(hipMalloc(&ln.d_waverows, sizeof(gsh::RowStat) * cells * static_cast<size_t>(std::max(a->split, 1)) * gsh::ONCHIP_MAX_WAVES));
+    if (a->split > 0 && gsh::onchip_dit(static_cast<int>(n)) && ln.d_z == nullptr) GSH_HIP(hipMalloc(&ln.d_z, sizeof(float2) * cells * n));
+    if (ln.d_results == nullptr) GSH_HIP(hipMalloc(&ln.d_results, sizeof(gsh::DevAcqResult) * P));
+    if (ln.d_arrivals == nullptr) GSH_HIP(hipMalloc(&ln.d_arrivals, sizeof(unsigned) * P));
+    GSH_HIP(hipMemset(ln.d_arrivals, 0, sizeof(unsigned) * P));
+    return GSH_OK;
+}
+
+void lane_free(gsh_acq::Lane& ln)
+{
+    if (ln.stream) (void)hipStreamSynchronize(ln.stream);
+    if (ln.d_spectra) (void)hipFree(ln.d_spectra);
+    if (ln.d_rows) (void)hipFree(ln.d_rows);
+    if (ln.d_subrows) (void)hipFree(ln.d_subrows);
+    if (ln.d_waverows) (void)hipFree(ln.d_waverows);
+    if (ln.d_z) (void)hipFree(ln.d_z);
+    if (ln.d_results) (void)hipFree(ln.d_results);
+    if (ln.d_arrivals) (void)hipFree(ln.d_arrivals);
+    if (ln.ev) (void)hipEventDestroy(ln.ev);
+    if (ln.ev_cells) (void)hipEventDestroy(ln.ev_cells);
+    if (ln.stream) (void)hipStreamDestroy(ln.stream);
+}
+
+// ---- the timing loops ----
+int check_timed(gsh_acq* a, uint32_t n_prn, int reps, int min_reps, const float* avg_ms)
+{
+    GSH_REQUIRE(a != nullptr && avg_ms != nullptr, "null argument");
+    if (reps < min_reps) return min_reps > 1 ? set_error(GSH_ERR_INVALID, "reps %d (need >= %d)", reps, min_reps) : set_error(GSH_ERR_INVALID, "reps %d", reps);
+    GSH_REQUIRE(n_prn >= 1 && n_prn <= a->conf.max_prn, "n_prn %u outside 1..%u", n_prn, a->conf.max_prn);
+    if (!a->have_input) return set_error(GSH_ERR_STATE, "no input block resident: call gsh_acq_dwell[_device] once first");
+    return GSH_OK;
+}
+
+// ev1 behind everything the handle's stream has been given, and the average over `reps` batches since ev0
+int stop_clock(gsh_acq* a, int reps, float* avg_ms)
+{
+    GSH_HIP(hipEventRecord(a->ev1, a->stream()));
+    GSH_HIP(hipEventSynchronize(a->ev1));
+    float ms = 0.0f;
+    GSH_HIP(hipEventElapsedTime(&ms, a->ev0, a->ev1));
+    *avg_ms = ms / static_cast<float>(reps);
     return GSH_OK;
 }
 
@@ -599,35 +759,28 @@ extern "C"
             return GSH_ERR_HIP;
         };
         hipError_t e;
-        if ((e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
+        if ((e = hipStreamCreateWithFlags(&a->lane[0].stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
         if ((e = hipMalloc(&a->d_bins_hz, sizeof(float) * D)) != hipSuccess) return fail(e, "hipMalloc(bins)");
         if (a->n_bins2 > 0 && (e = hipMalloc(&a->d_bins2_hz, sizeof(float) * a->n_bins2 * P)) != hipSuccess) return fail(e, "hipMalloc(bins2)");
         const size_t in_len = std::max<size_t>(n, c.consumed_samples);  // fold > 1: the block is longer than the transform
         if ((e = hipMalloc(&a->d_in, sizeof(float2) * in_len)) != hipSuccess) return fail(e, "hipMalloc(in)");
-        if ((e = hipMalloc(&a->d_spectra, sizeof(float2) * D * n)) != hipSuccess) return fail(e, "hipMalloc(spectra)");
+        // (lane 0's spectra here, ahead of lane_alloc, which fills the empty slots only: the handle's buffers keep the order of allocation they always had)
+        if ((e = hipMalloc(&a->lane[0].d_spectra, sizeof(float2) * D * n)) != hipSuccess) return fail(e, "hipMalloc(spectra)");
         if ((e = hipMalloc(&a->d_codes, sizeof(float2) * P * n)) != hipSuccess) return fail(e, "hipMalloc(codes)");
         // the four-step path keeps its inter-pass intermediate in HBM; the on-chip path only needs one row to stage a code
         const size_t tmp_rows = a->onchip ? size_t(1) : std::max(chunk * D, size_t(2));
         if ((e = hipMalloc(&a->d_tmp, sizeof(float2) * tmp_rows * n)) != hipSuccess) return fail(e, "hipMalloc(tmp)");
-        const bool need_grid = !(a->onchip && c.no_grid) || (a->split > 0 && !c.use_cfar);
-        if (need_grid)
+        if (!a->onchip || stores_grid(a))  // (the four-step kernels always go through the grid)
             {
                 if ((e = hipMalloc(&a->d_grid, sizeof(float) * P * D * eff)) != hipSuccess) return fail(e, "hipMalloc(grid)");
                 if ((e = hipMemset(a->d_grid, 0, sizeof(float) * P * D * eff)) != hipSuccess) return fail(e, "hipMemset(grid)");
             }
-        if ((e = hipMalloc(&a->d_rows, sizeof(gsh::RowStat) * P * D)) != hipSuccess) return fail(e, "hipMalloc(rows)");
-        if (a->split > 0 && (e = hipMalloc(&a->d_subrows, sizeof(gsh::RowStat) * P * std::max<size_t>(D, a->n_bins2) * a->split)) != hipSuccess)
-            return fail(e, "hipMalloc(subrows)");
-        if (a->onchip && (e = hipMalloc(&a->d_waverows, sizeof(gsh::RowStat) * P * std::max<size_t>(D, a->n_bins2) * static_cast<size_t>(std::max(a->split, 1)) * gsh::ONCHIP_MAX_WAVES)) != hipSuccess)
-            return fail(e, "hipMalloc(wave records)");
-        if (a->split > 0 && gsh::onchip_dit(static_cast<int>(n)))
+        rc = lane_alloc(a, a->lane[0], std::max<size_t>(D, a->n_bins2));  // (step two's batches: n_bins2 bins per listed slot)
+        if (rc != GSH_OK)
             {
-                const size_t cells = P * std::max<size_t>(D, a->n_bins2);
-                if ((e = hipMalloc(&a->d_z, sizeof(float2) * cells * n)) != hipSuccess) return fail(e, "hipMalloc(sub-cell transforms)");
+                gsh_acq_destroy(a);
+                return rc;
             }
-        if ((e = hipMalloc(&a->d_results, sizeof(gsh::DevAcqResult) * P)) != hipSuccess) return fail(e, "hipMalloc(results)");
-        if ((e = hipMalloc(&a->d_arrivals, sizeof(unsigned) * P)) != hipSuccess) return fail(e, "hipMalloc(arrivals)");
-        if ((e = hipMemset(a->d_arrivals, 0, sizeof(unsigned) * P)) != hipSuccess) return fail(e, "hipMemset(arrivals)");
         if ((e = hipHostMalloc(reinterpret_cast<void**>(&a->h_results), sizeof(gsh::DevAcqResult) * P, hipHostMallocDefault)) != hipSuccess) return fail(e, "hipHostMalloc");
         if ((e = hipHostMalloc(reinterpret_cast<void**>(&a->h_stage), sizeof(float2) * in_len, hipHostMallocDefault)) != hipSuccess) return fail(e, "hipHostMalloc");
         if ((e = hipEventCreate(&a->ev0)) != hipSuccess) return fail(e, "hipEventCreate");
@@ -647,7 +800,7 @@ extern "C"
     {
         if (!a) return;
         (void)hipSetDevice(a->device);
-        if (a->stream) (void)hipStreamSynchronize(a->stream);
+        if (a->stream()) (void)hipStreamSynchronize(a->stream());
         gsh::plan_destroy(&a->plan);
         if (a->d_bins_hz) (void)hipFree(a->d_bins_hz);
         if (a->d_bins2_hz) (void)hipFree(a->d_bins2_hz);
@@ -657,39 +810,16 @@ extern "C"
         if (a->d_tc_delays) (void)hipFree(a->d_tc_delays);
         if (a->d_tc_out) (void)hipFree(a->d_tc_out);
         if (a->d_in) (void)hipFree(a->d_in);
-        if (a->d_spectra) (void)hipFree(a->d_spectra);
         if (a->d_codes) (void)hipFree(a->d_codes);
         if (a->d_codes_sel) (void)hipFree(a->d_codes_sel);
         if (a->d_tmp) (void)hipFree(a->d_tmp);
         if (a->d_grid) (void)hipFree(a->d_grid);
-        if (a->d_rows) (void)hipFree(a->d_rows);
-        if (a->d_subrows) (void)hipFree(a->d_subrows);
-        if (a->d_waverows) (void)hipFree(a->d_waverows);
-        if (a->d_z) (void)hipFree(a->d_z);
         if (a->d_pair) (void)hipFree(a->d_pair);
-        if (a->d_results) (void)hipFree(a->d_results);
-        if (a->d_arrivals) (void)hipFree(a->d_arrivals);
         if (a->h_results) (void)hipHostFree(a->h_results);
         if (a->h_stage) (void)hipHostFree(a->h_stage);
         if (a->ev0) (void)hipEventDestroy(a->ev0);
         if (a->ev1) (void)hipEventDestroy(a->ev1);
-        for (int l = 0; l < gsh_acq::MAX_LANES; l++)
-            if (a->lane[l].ev_cells) (void)hipEventDestroy(a->lane[l].ev_cells);
-        for (int l = 1; l < gsh_acq::MAX_LANES; l++)
-            {
-                gsh_acq::Lane& ln = a->lane[l];
-                if (ln.stream) (void)hipStreamSynchronize(ln.stream);
-                if (ln.d_spectra) (void)hipFree(ln.d_spectra);
-                if (ln.d_rows) (void)hipFree(ln.d_rows);
-                if (ln.d_subrows) (void)hipFree(ln.d_subrows);
-                if (ln.d_waverows) (void)hipFree(ln.d_waverows);
-                if (ln.d_z) (void)hipFree(ln.d_z);
-                if (ln.d_results) (void)hipFree(ln.d_results);
-                if (ln.d_arrivals) (void)hipFree(ln.d_arrivals);
-                if (ln.ev) (void)hipEventDestroy(ln.ev);
-                if (ln.stream) (void)hipStreamDestroy(ln.stream);
-            }
-        if (a->stream) (void)hipStreamDestroy(a->stream);
+        for (int l = gsh_acq::MAX_LANES - 1; l >= 0; l--) lane_free(a->lane[l]);  // (the handle's own stream last)
         delete a;
     }
 
@@ -699,64 +829,39 @@ extern "C"
         GSH_REQUIRE(prn_slot < a->conf.max_prn, "prn_slot %u outside 0..%u", prn_slot, a->conf.max_prn - 1);
         GSH_HIP(hipSetDevice(a->device));
         const gsh_acq_conf& c = a->conf;
-        // placement rules of acq.cc:230-247
-        int n_in, place_off;
+        // what is staged, and where the transform places it: the rules of acq.cc:230-247
+        int n_in, place_off = 0;
         if (a->padded)
             {
                 // the code twice, back to back: lag -tau of the linear correlation with [c c] is lag tau of the circular one with c
                 const size_t N = a->logical_n;
                 std::memcpy(a->h_stage, code_iq, sizeof(float2) * N);
                 std::memcpy(a->h_stage + N, code_iq, sizeof(float2) * N);
-                float2* d_code_time = a->d_tmp + static_cast<size_t>(c.fft_size);
-                if (a->n_bins < 2) d_code_time = a->d_spectra;
-                GSH_HIP(hipMemcpyAsync(d_code_time, a->h_stage, sizeof(float2) * 2 * N, hipMemcpyHostToDevice, a->stream));
-                int rcp = gsh::fft_forward(a->plan, d_code_time, 0, static_cast<int>(2 * N), 0, nullptr, 1.0, a->d_tmp, a->d_codes + static_cast<size_t>(prn_slot) * c.fft_size, 1,
-                    a->stream);
-                if (rcp != GSH_OK) return rcp;
-                GSH_HIP(hipStreamSynchronize(a->stream));
-                a->code_set[prn_slot] = 1;
-                return GSH_OK;
-            }
-        if (c.bit_transition_flag)
-            {
-                n_in = static_cast<int>(c.fft_size / 2);
-                place_off = static_cast<int>(c.fft_size / 2);
-            }
-        else if (c.consumed_samples == c.fft_size || c.fold > 1)
-            {
-                n_in = static_cast<int>(c.fft_size);  // fold > 1: the caller hands over the code already folded to fft_size (quicksync.cc:137-152)
-                place_off = 0;
+                n_in = static_cast<int>(2 * N);
             }
         else
             {
-                n_in = static_cast<int>(c.consumed_samples);
-                place_off = static_cast<int>(c.fft_size - c.consumed_samples);
+                if (c.bit_transition_flag)
+                    n_in = place_off = static_cast<int>(c.fft_size / 2);
+                else if (c.consumed_samples == c.fft_size || c.fold > 1)
+                    n_in = static_cast<int>(c.fft_size);  // fold > 1: the caller hands over the code already folded to fft_size (quicksync.cc:137-152)
+                else
+                    {
+                        n_in = static_cast<int>(c.consumed_samples);
+                        place_off = static_cast<int>(c.fft_size - c.consumed_samples);
+                    }
+                std::memcpy(a->h_stage, code_iq, sizeof(float2) * static_cast<size_t>(n_in));
             }
-        std::memcpy(a->h_stage, code_iq, sizeof(float2) * static_cast<size_t>(n_in));
-        if (a->onchip)
-            {
-                GSH_HIP(hipMemcpyAsync(a->d_tmp, a->h_stage, sizeof(float2) * static_cast<size_t>(n_in), hipMemcpyHostToDevice, a->stream));
-                int rc1 = gsh::onchip_forward(static_cast<int>(c.fft_size), a->d_tmp, 0, n_in, place_off, nullptr, 1.0,
-                    a->d_codes + static_cast<size_t>(prn_slot) * c.fft_size, 1, a->stream);
-                if (rc1 != GSH_OK) return rc1;
-                GSH_HIP(hipStreamSynchronize(a->stream));
-                a->code_set[prn_slot] = 1;
-                return GSH_OK;
-            }
-        // stage the time-domain replica in d_tmp's tail-free area: d_in is reserved for the signal, so use d_spectra[0] row
-        // as scratch input is unsafe while a dwell is queued; everything here is on one stream, so order is preserved.
-        float2* d_code_time = a->d_tmp + static_cast<size_t>(c.fft_size);  // second row of tmp (tmp holds >= n_bins rows)
-        float2* d_scratch = a->d_tmp;                                      // first row: column-pass output
-        if (a->n_bins < 2)
-            {
-                // tmp has a single row: borrow the grid-independent spectra buffer instead
-                d_code_time = a->d_spectra;
-            }
-        GSH_HIP(hipMemcpyAsync(d_code_time, a->h_stage, sizeof(float2) * static_cast<size_t>(n_in), hipMemcpyHostToDevice, a->stream));
-        int rc = gsh::fft_forward(a->plan, d_code_time, 0, n_in, place_off, nullptr, 1.0, d_scratch,
-            a->d_codes + static_cast<size_t>(prn_slot) * c.fft_size, 1, a->stream);
+        // where the time-domain replica waits for its transform (d_in is reserved for the signal; everything here is on one stream, so order is preserved):
+        // on-chip, d_tmp's one row; four-step, the second row of d_tmp -- the first is the column pass's output --, or, where the Doppler grid has a single
+        // bin, the spectra buffer
+        float2* d_code_time = a->onchip ? a->d_tmp : (a->n_bins < 2 ? a->lane[0].d_spectra : a->d_tmp + static_cast<size_t>(c.fft_size));
+        float2* d_code = a->d_codes + static_cast<size_t>(prn_slot) * c.fft_size;
+        GSH_HIP(hipMemcpyAsync(d_code_time, a->h_stage, sizeof(float2) * static_cast<size_t>(n_in), hipMemcpyHostToDevice, a->stream()));
+        const int rc = a->onchip ? gsh::onchip_forward(static_cast<int>(c.fft_size), d_code_time, 0, n_in, place_off, nullptr, 1.0, d_code, 1, a->stream())
+                                 : gsh::fft_forward(a->plan, d_code_time, 0, n_in, place_off, nullptr, 1.0, a->d_tmp, d_code, 1, a->stream());
         if (rc != GSH_OK) return rc;
-        GSH_HIP(hipStreamSynchronize(a->stream));
+        GSH_HIP(hipStreamSynchronize(a->stream()));
         a->code_set[prn_slot] = 1;
         return GSH_OK;
     }
@@ -803,11 +908,11 @@ extern "C"
         if (!a->have_input) return set_error(GSH_ERR_STATE, "no input block has been handed to this handle yet");
         GSH_HIP(hipSetDevice(a->device));
         if (a->d_power == nullptr) GSH_HIP(hipMalloc(&a->d_power, sizeof(double)));
-        hipLaunchKernelGGL(input_power_kernel, dim3(1), dim3(1024), 0, a->stream, a->d_in, static_cast<int>(a->conf.consumed_samples), a->d_power);
+        hipLaunchKernelGGL(input_power_kernel, dim3(1), dim3(1024), 0, a->stream(), a->d_in, static_cast<int>(a->conf.consumed_samples), a->d_power);
         GSH_HIP(hipGetLastError());
         double sum = 0.0;
-        GSH_HIP(hipMemcpyAsync(&sum, a->d_power, sizeof(double), hipMemcpyDeviceToHost, a->stream));
-        GSH_HIP(hipStreamSynchronize(a->stream));
+        GSH_HIP(hipMemcpyAsync(&sum, a->d_power, sizeof(double), hipMemcpyDeviceToHost, a->stream()));
+        GSH_HIP(hipStreamSynchronize(a->stream()));
         // pcps_tong_acquisition_cc.cc:208-210: float sum of float |x|^2, then / (float) fft_size
         *mean_power = static_cast<float>(sum) / static_cast<float>(a->conf.consumed_samples);
         return GSH_OK;
@@ -815,26 +920,22 @@ extern "C"
 
     int gsh_acq_dwell_device(gsh_acq_t* a, const void* device_in_iq, uint32_t n_prn, int accumulate, uint32_t dwell_count, gsh_acq_result* results)
     {
-        int rc = check_dwell_args(a, n_prn, results);
-        if (rc == GSH_OK) rc = check_accumulate(a, accumulate);
+        int rc = check_dwell(a, n_prn, accumulate, results);
         if (rc != GSH_OK) return rc;
         GSH_REQUIRE(device_in_iq != nullptr, "null input");
         GSH_HIP(hipSetDevice(a->device));
-        GSH_HIP(hipMemcpyAsync(a->d_in, device_in_iq, sizeof(float2) * a->conf.consumed_samples, hipMemcpyDeviceToDevice, a->stream));
-        a->have_input = true;
-        rc = enqueue_dwell(a, n_prn, accumulate, dwell_count);
+        rc = take_device(a, device_in_iq);
         if (rc != GSH_OK) return rc;
-        return finish_results(a, n_prn, results);
+        return run_dwell(a, whole_batch(a, n_prn, accumulate, dwell_count), results);
     }
 
     int gsh_acq_stage_input(gsh_acq_t* a, const float* in_iq)
     {
         GSH_REQUIRE(a != nullptr && in_iq != nullptr, "null argument");
         GSH_HIP(hipSetDevice(a->device));
-        std::memcpy(a->h_stage, in_iq, sizeof(float2) * a->conf.consumed_samples);
-        GSH_HIP(hipMemcpyAsync(a->d_in, a->h_stage, sizeof(float2) * a->conf.consumed_samples, hipMemcpyHostToDevice, a->stream));
-        GSH_HIP(hipStreamSynchronize(a->stream));  // h_stage may be rewritten by the next call
-        a->have_input = true;
+        const int rc = take_host(a, in_iq);
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipStreamSynchronize(a->stream()));  // no results are waited for here, and the next call may rewrite h_stage while the copy still reads it
         return GSH_OK;
     }
 
@@ -842,21 +943,16 @@ extern "C"
     {
         GSH_REQUIRE(a != nullptr && device_in_iq != nullptr, "null argument");
         GSH_HIP(hipSetDevice(a->device));
-        GSH_HIP(hipMemcpyAsync(a->d_in, device_in_iq, sizeof(float2) * a->conf.consumed_samples, hipMemcpyDeviceToDevice, a->stream));
-        a->have_input = true;
-        return GSH_OK;
+        return take_device(a, device_in_iq);
     }
 
     int gsh_acq_dwell_resident(gsh_acq_t* a, uint32_t n_prn, int accumulate, uint32_t dwell_count, gsh_acq_result* results)
     {
-        int rc = check_dwell_args(a, n_prn, results);
-        if (rc == GSH_OK) rc = check_accumulate(a, accumulate);
+        const int rc = check_dwell(a, n_prn, accumulate, results);
         if (rc != GSH_OK) return rc;
         if (!a->have_input) return set_error(GSH_ERR_STATE, "no input block resident: call gsh_acq_stage_input[_device] first");
         GSH_HIP(hipSetDevice(a->device));
-        rc = enqueue_dwell(a, n_prn, accumulate, dwell_count);
-        if (rc != GSH_OK) return rc;
-        return finish_results(a, n_prn, results);
+        return run_dwell(a, whole_batch(a, n_prn, accumulate, dwell_count), results);
     }
 
     int gsh_acq_dwell_ring(gsh_acq_t* a, gsh_stream_t* ring, uint64_t first_sample, uint32_t n_prn, int accumulate, uint32_t dwell_count,
@@ -868,85 +964,64 @@ extern "C"
         int rc = gsh::stream_window(ring, first_sample, a->conf.consumed_samples, &w);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipSetDevice(a->device));
-        if (ring->pushed != nullptr) GSH_HIP(hipStreamWaitEvent(a->stream, ring->pushed, 0));  // conversions queued by gsh_stream_push_device
+        if (ring->pushed != nullptr) GSH_HIP(hipStreamWaitEvent(a->stream(), ring->pushed, 0));  // conversions queued by gsh_stream_push_device
         rc = gsh_acq_dwell_device(a, w, n_prn, accumulate, dwell_count, results);
         if (rc != GSH_OK) return rc;
-        return gsh::stream_mark_read(ring, first_sample, a->stream);  // (the dwell has already been waited for when results were asked for; harmless otherwise)
+        return gsh::stream_mark_read(ring, first_sample, a->stream());  // (the dwell has already been waited for when results were asked for; harmless otherwise)
     }
 
     int gsh_acq_dwell(gsh_acq_t* a, const float* in_iq, uint32_t n_prn, int accumulate, uint32_t dwell_count, gsh_acq_result* results)
     {
-        int rc = check_dwell_args(a, n_prn, results);
-        if (rc == GSH_OK) rc = check_accumulate(a, accumulate);
+        int rc = check_dwell(a, n_prn, accumulate, results);
         if (rc != GSH_OK) return rc;
         GSH_REQUIRE(in_iq != nullptr, "null input");
         GSH_HIP(hipSetDevice(a->device));
-        std::memcpy(a->h_stage, in_iq, sizeof(float2) * a->conf.consumed_samples);
-        GSH_HIP(hipMemcpyAsync(a->d_in, a->h_stage, sizeof(float2) * a->conf.consumed_samples, hipMemcpyHostToDevice, a->stream));
-        a->have_input = true;
-        rc = enqueue_dwell(a, n_prn, accumulate, dwell_count);
+        rc = take_host(a, in_iq);
         if (rc != GSH_OK) return rc;
-        return finish_results(a, n_prn, results);
+        return run_dwell(a, whole_batch(a, n_prn, accumulate, dwell_count), results);
     }
 
     int gsh_acq_dwell_slots(gsh_acq_t* a, const float* in_iq, uint32_t n, const uint32_t* prn_slots, gsh_acq_result* results)
     {
         GSH_REQUIRE(a != nullptr && in_iq != nullptr && prn_slots != nullptr && results != nullptr, "null argument");
         GSH_REQUIRE(n >= 1 && n <= a->conf.max_prn, "n %u outside 1..%u", n, a->conf.max_prn);
-        bool prefix = true;
-        for (uint32_t i = 0; i < n; i++)
-            {
-                GSH_REQUIRE(prn_slots[i] < a->conf.max_prn, "prn slot %u outside 0..%u", prn_slots[i], a->conf.max_prn - 1);
-                if (!a->code_set[prn_slots[i]]) return set_error(GSH_ERR_STATE, "local code of prn slot %u has not been set (set_local_code)", prn_slots[i]);
-                prefix = prefix && prn_slots[i] == i;
-            }
+        int rc = check_slots(a, n, prn_slots, nullptr);
+        if (rc != GSH_OK) return rc;
         GSH_HIP(hipSetDevice(a->device));
-        const size_t len = a->conf.fft_size;
-        float2* const all_codes = a->d_codes;
+        Batch b = whole_batch(a, n, 0, 1u);
+        bool prefix = true;
+        for (uint32_t i = 0; i < n; i++) prefix = prefix && prn_slots[i] == i;
         if (!prefix)
             {
                 // the batch's code spectra side by side (a few hundred KB each, device to device): the kernels then see an ordinary batch of n codes
+                const size_t len = a->conf.fft_size;
                 if (a->d_codes_sel == nullptr) GSH_HIP(hipMalloc(&a->d_codes_sel, sizeof(float2) * len * a->conf.max_prn));
                 for (uint32_t i = 0; i < n; i++)
-                    GSH_HIP(hipMemcpyAsync(a->d_codes_sel + static_cast<size_t>(i) * len, all_codes + static_cast<size_t>(prn_slots[i]) * len, sizeof(float2) * len,
-                        hipMemcpyDeviceToDevice, a->stream));
+                    GSH_HIP(hipMemcpyAsync(a->d_codes_sel + static_cast<size_t>(i) * len, a->d_codes + static_cast<size_t>(prn_slots[i]) * len, sizeof(float2) * len,
+                        hipMemcpyDeviceToDevice, a->stream()));
+                b.codes = a->d_codes_sel;
             }
-        std::memcpy(a->h_stage, in_iq, sizeof(float2) * a->conf.consumed_samples);
-        GSH_HIP(hipMemcpyAsync(a->d_in, a->h_stage, sizeof(float2) * a->conf.consumed_samples, hipMemcpyHostToDevice, a->stream));
-        a->have_input = true;
-        if (!prefix) a->d_codes = a->d_codes_sel;
-        int rc = enqueue_dwell(a, n, 0, 1u);
-        a->d_codes = all_codes;
+        rc = take_host(a, in_iq);
         if (rc != GSH_OK) return rc;
-        return finish_results(a, n, results);
+        return run_dwell(a, b, results);
     }
 
     int gsh_acq_dwell_cshort(gsh_acq_t* a, const int16_t* in_iq16, uint32_t n_prn, int accumulate, uint32_t dwell_count, gsh_acq_result* results)
     {
-        int rc = check_dwell_args(a, n_prn, results);
-        if (rc == GSH_OK) rc = check_accumulate(a, accumulate);
+        int rc = check_dwell(a, n_prn, accumulate, results);
         if (rc != GSH_OK) return rc;
         GSH_REQUIRE(in_iq16 != nullptr, "null input");
         GSH_HIP(hipSetDevice(a->device));
-        const size_t n = a->conf.consumed_samples;
-        if (a->d_in16 == nullptr) GSH_HIP(hipMalloc(&a->d_in16, sizeof(int16_t) * 2 * n));
-        // h_stage holds fft_size complex64 = room for 4 * fft_size int16
-        std::memcpy(a->h_stage, in_iq16, sizeof(int16_t) * 2 * n);
-        GSH_HIP(hipMemcpyAsync(a->d_in16, a->h_stage, sizeof(int16_t) * 2 * n, hipMemcpyHostToDevice, a->stream));
-        rc = gsh::convert_to_complex(a->d_in16, GSH_ITEM_SHORT, 0, a->d_in, n, a->stream);  // acq.cc:653-656
+        rc = take_cshort(a, in_iq16);
         if (rc != GSH_OK) return rc;
-        a->have_input = true;
-        rc = enqueue_dwell(a, n_prn, accumulate, dwell_count);
-        if (rc != GSH_OK) return rc;
-        return finish_results(a, n_prn, results);
+        return run_dwell(a, whole_batch(a, n_prn, accumulate, dwell_count), results);
     }
 
+    // step two, input already in d_in: one batch of n_bins2 bins per listed slot, each into the first rows of its slot's grid and into record i of lane 0
     static int dwell_step2_common(gsh_acq_t* a, uint32_t n, const uint32_t* prn_slots, const float* centers, const float* powers, int accumulate,
         uint32_t dwell_count, gsh_acq_result* results)
     {
         const gsh_acq_conf& c = a->conf;
-        const int nfft = static_cast<int>(c.fft_size);
-        const int eff = static_cast<int>(c.effective_fft_size);
         const int D2 = a->n_bins2;
         const float half = static_cast<float>(std::floor(static_cast<double>(D2) / 2.0));  // acq.cc:298
         for (uint32_t i = 0; i < n; i++)
@@ -955,60 +1030,32 @@ extern "C"
                     const float doppler = (static_cast<float>(d) - half) * c.doppler_step2;    // acq.cc:298
                     a->h_bins2_hz[static_cast<size_t>(i) * D2 + d] = centers[i] + doppler;     // acq.cc:299
                 }
-        GSH_HIP(hipMemcpyAsync(a->d_bins2_hz, a->h_bins2_hz.data(), sizeof(float) * D2 * n, hipMemcpyHostToDevice, a->stream));
-        const size_t grid_per_prn = static_cast<size_t>(a->n_bins) * eff;
+        GSH_HIP(hipMemcpyAsync(a->d_bins2_hz, a->h_bins2_hz.data(), sizeof(float) * D2 * n, hipMemcpyHostToDevice, a->stream()));
+        const size_t grid_per_prn = static_cast<size_t>(a->n_bins) * c.effective_fft_size;
+        Batch b = whole_batch(a, 1, accumulate, dwell_count);
+        b.n_bins = D2;
         for (uint32_t i = 0; i < n; i++)
             {
                 const uint32_t slot = prn_slots[i];
-                const float* bins = a->d_bins2_hz + static_cast<size_t>(i) * D2;
-                float* grid = a->d_grid ? a->d_grid + slot * grid_per_prn : nullptr;  // rows 0..D2-1 of the PRN's grid (acq.cc:526 reuses d_magnitude_grid)
-                int rc;
-                if (a->onchip)
-                    {
-                        rc = gsh::onchip_forward(nfft, a->d_in, 0, static_cast<int>(c.consumed_samples), 0, bins, static_cast<double>(c.fs_in), a->d_spectra, D2,
-                            a->stream);
-                        if (rc != GSH_OK) return rc;
-                        rc = gsh::onchip_correlate(nfft, a->d_spectra, a->d_codes + static_cast<size_t>(slot) * nfft, grid, a->d_rows + static_cast<size_t>(i) * D2,
-                            a->d_subrows ? a->d_subrows + static_cast<size_t>(i) * D2 * a->split : nullptr,
-                            a->d_results + i, a->d_arrivals + i, 1, D2, c.bit_transition_flag ? eff : 0, eff, accumulate, (c.no_grid && !(a->split > 0 && !c.use_cfar)) ? 0 : 1, static_cast<int>(c.samples_per_chip), c.use_cfar,
-                            dwell_count ? dwell_count : 1u, a->grid_weight, a->stream, a->d_z ? a->d_z + static_cast<size_t>(i) * D2 * nfft : nullptr,
-                            a->d_waverows + static_cast<size_t>(i) * D2 * static_cast<size_t>(std::max(a->split, 1)) * gsh::ONCHIP_MAX_WAVES);
-                    }
-                else
-                    {
-                        rc = gsh::fft_forward(a->plan, a->d_in, 0, static_cast<int>(c.consumed_samples), 0, bins, static_cast<double>(c.fs_in), a->d_tmp,
-                            a->d_spectra, D2, a->stream);
-                        if (rc != GSH_OK) return rc;
-                        rc = gsh::correlate_grid(a->plan, a->d_spectra, a->d_codes + static_cast<size_t>(slot) * nfft, a->d_tmp, grid, 1, D2,
-                            c.bit_transition_flag ? eff : 0, eff, accumulate, a->grid_weight, a->stream);
-                        if (rc != GSH_OK) return rc;
-                        rc = gsh::grid_statistics(grid, a->d_rows + static_cast<size_t>(i) * D2, a->d_results + i, 1, D2, eff, static_cast<int>(c.samples_per_chip),
-                            c.use_cfar, dwell_count ? dwell_count : 1u, a->stream);
-                    }
+                b.codes = a->d_codes + static_cast<size_t>(slot) * c.fft_size;
+                b.bins = a->d_bins2_hz + static_cast<size_t>(i) * D2;
+                b.grid = a->d_grid ? a->d_grid + slot * grid_per_prn : nullptr;  // rows 0..D2-1 of the PRN's grid (acq.cc:526 reuses d_magnitude_grid)
+                b.first = i;
+                const int rc = run_batch(a, b);
                 if (rc != GSH_OK) return rc;
             }
-        GSH_HIP(hipMemcpyAsync(a->h_results, a->d_results, sizeof(gsh::DevAcqResult) * n, hipMemcpyDeviceToHost, a->stream));
-        GSH_HIP(hipStreamSynchronize(a->stream));
+        const int rc = fetch_results(a, n);
+        if (rc != GSH_OK) return rc;
         for (uint32_t i = 0; i < n; i++)
             {
                 const gsh::DevAcqResult& r = a->h_results[i];
                 gsh_acq_result& o = results[i];
-                o.index_time = r.index_time;
-                o.index_doppler = r.index_doppler;
-                o.doppler_hz = static_cast<int32_t>(centers[i] + (static_cast<float>(r.index_doppler) - half) * c.doppler_step2);  // acq.cc:436 / :481
-                o.acq_delay_samples = std::fmod(static_cast<float>(r.index_time), c.samples_per_code);
-                o.peak = r.peak;
-                o.second_peak = r.second_peak;
+                to_result(c, r, static_cast<int32_t>(centers[i] + (static_cast<float>(r.index_doppler) - half) * c.doppler_step2), o);  // acq.cc:436 / :481
                 if (c.use_cfar)
                     {
                         // acq.cc:428-445: d_input_power is NOT recomputed in step two; the statistic divides by step one's value
                         o.input_power = powers[i];
                         o.test_statistics = (powers[i] < std::numeric_limits<float>::epsilon()) ? 0.0f : r.peak / powers[i];
-                    }
-                else
-                    {
-                        o.input_power = r.input_power;
-                        o.test_statistics = r.test_statistics;
                     }
             }
         return GSH_OK;
@@ -1021,13 +1068,8 @@ extern "C"
         if (a->n_bins2 <= 0) return set_error(GSH_ERR_STATE, "the handle was created with num_doppler_bins_step2 = 0 (make_two_steps off)");
         GSH_REQUIRE(n >= 1 && n <= a->conf.max_prn, "n %u outside 1..%u", n, a->conf.max_prn);
         GSH_REQUIRE(!a->conf.use_cfar || powers != nullptr, "the CFAR statistic of step two needs step one's input power (acq.cc:428-445)");
-        for (uint32_t i = 0; i < n; i++)
-            {
-                GSH_REQUIRE(prn_slots[i] < a->conf.max_prn, "prn slot %u outside 0..%u", prn_slots[i], a->conf.max_prn - 1);
-                if (!a->code_set[prn_slots[i]]) return set_error(GSH_ERR_STATE, "local code of prn slot %u has not been set (set_local_code)", prn_slots[i]);
-                GSH_REQUIRE(std::isfinite(centers[i]), "doppler_center_step_two[%u] is not finite", i);
-                for (uint32_t k = 0; k < i; k++) GSH_REQUIRE(prn_slots[k] != prn_slots[i], "prn slot %u listed twice", prn_slots[i]);
-            }
+        const int rc = check_slots(a, n, prn_slots, centers);
+        if (rc != GSH_OK) return rc;
         return check_accumulate(a, accumulate);
     }
 
@@ -1037,8 +1079,8 @@ extern "C"
         int rc = check_step2_args(a, device_in_iq, n, prn_slots, doppler_center_step_two, input_power_step_one, accumulate, results);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipSetDevice(a->device));
-        GSH_HIP(hipMemcpyAsync(a->d_in, device_in_iq, sizeof(float2) * a->conf.consumed_samples, hipMemcpyDeviceToDevice, a->stream));
-        a->have_input = true;
+        rc = take_device(a, device_in_iq);
+        if (rc != GSH_OK) return rc;
         return dwell_step2_common(a, n, prn_slots, doppler_center_step_two, input_power_step_one, accumulate, dwell_count, results);
     }
 
@@ -1048,9 +1090,8 @@ extern "C"
         int rc = check_step2_args(a, in_iq, n, prn_slots, doppler_center_step_two, input_power_step_one, accumulate, results);
         if (rc != GSH_OK) return rc;
         GSH_HIP(hipSetDevice(a->device));
-        std::memcpy(a->h_stage, in_iq, sizeof(float2) * a->conf.consumed_samples);
-        GSH_HIP(hipMemcpyAsync(a->d_in, a->h_stage, sizeof(float2) * a->conf.consumed_samples, hipMemcpyHostToDevice, a->stream));
-        a->have_input = true;
+        rc = take_host(a, in_iq);
+        if (rc != GSH_OK) return rc;
         return dwell_step2_common(a, n, prn_slots, doppler_center_step_two, input_power_step_one, accumulate, dwell_count, results);
     }
 
@@ -1061,8 +1102,8 @@ extern "C"
         if (a->d_grid == nullptr) return set_error(GSH_ERR_STATE, "the handle was created with no_grid = 1: no grid is stored");
         GSH_HIP(hipSetDevice(a->device));
         const size_t row = static_cast<size_t>(a->n_bins) * a->conf.effective_fft_size;
-        GSH_HIP(hipMemcpyAsync(grid, a->d_grid + prn_slot * row, sizeof(float) * row, hipMemcpyDeviceToHost, a->stream));
-        GSH_HIP(hipStreamSynchronize(a->stream));
+        GSH_HIP(hipMemcpyAsync(grid, a->d_grid + prn_slot * row, sizeof(float) * row, hipMemcpyDeviceToHost, a->stream()));
+        GSH_HIP(hipStreamSynchronize(a->stream()));
         return GSH_OK;
     }
 
@@ -1073,9 +1114,9 @@ extern "C"
         if (!a->have_input) return set_error(GSH_ERR_STATE, "no dwell has run on this handle yet");
         GSH_HIP(hipSetDevice(a->device));
         std::vector<gsh::RowStat> rows(static_cast<size_t>(a->n_bins));
-        GSH_HIP(hipMemcpyAsync(rows.data(), a->d_rows + static_cast<size_t>(prn_slot) * a->n_bins, sizeof(gsh::RowStat) * a->n_bins, hipMemcpyDeviceToHost,
-            a->stream));
-        GSH_HIP(hipStreamSynchronize(a->stream));
+        GSH_HIP(hipMemcpyAsync(rows.data(), a->lane[0].d_rows + static_cast<size_t>(prn_slot) * a->n_bins, sizeof(gsh::RowStat) * a->n_bins, hipMemcpyDeviceToHost,
+            a->stream()));
+        GSH_HIP(hipStreamSynchronize(a->stream()));
         for (int d = 0; d < a->n_bins; d++)
             {
                 row_peak[d] = rows[static_cast<size_t>(d)].maxv;
@@ -1098,7 +1139,7 @@ extern "C"
         if (a->d_pair == nullptr) GSH_HIP(hipMalloc(&a->d_pair, sizeof(gsh_acq_pair_peak) * a->n_bins));
         PairPeakArgs k;
         k.grid = a->d_grid;
-        k.rows = a->d_rows;
+        k.rows = a->lane[0].d_rows;
         k.n = static_cast<int>(a->conf.effective_fft_size);
         k.n_bins = a->n_bins;
         k.ia = slot_ia;
@@ -1108,10 +1149,10 @@ extern "C"
         const float fnf = static_cast<float>(a->padded ? a->logical_n : a->conf.fft_size) * static_cast<float>(a->padded ? a->logical_n : a->conf.fft_size);
         k.divisor = fnf * fnf;
         k.out = a->d_pair;
-        hipLaunchKernelGGL(pair_peaks_kernel, dim3(a->n_bins), dim3(1024), 0, a->stream, k);
+        hipLaunchKernelGGL(pair_peaks_kernel, dim3(a->n_bins), dim3(1024), 0, a->stream(), k);
         GSH_HIP(hipGetLastError());
-        GSH_HIP(hipMemcpyAsync(out, a->d_pair, sizeof(gsh_acq_pair_peak) * a->n_bins, hipMemcpyDeviceToHost, a->stream));
-        GSH_HIP(hipStreamSynchronize(a->stream));
+        GSH_HIP(hipMemcpyAsync(out, a->d_pair, sizeof(gsh_acq_pair_peak) * a->n_bins, hipMemcpyDeviceToHost, a->stream()));
+        GSH_HIP(hipStreamSynchronize(a->stream()));
         return GSH_OK;
     }
 
@@ -1137,87 +1178,54 @@ extern "C"
             }
         if (a->d_tc_delays == nullptr) GSH_HIP(hipMalloc(&a->d_tc_delays, sizeof(uint32_t) * TC_MAX_DELAYS));
         if (a->d_tc_out == nullptr) GSH_HIP(hipMalloc(&a->d_tc_out, sizeof(float2) * TC_MAX_DELAYS));
-        GSH_HIP(hipMemcpyAsync(a->d_tc_code, code_iq, sizeof(float2) * code_len, hipMemcpyHostToDevice, a->stream));
-        GSH_HIP(hipMemcpyAsync(a->d_tc_delays, delays, sizeof(uint32_t) * n_delays, hipMemcpyHostToDevice, a->stream));
-        hipLaunchKernelGGL(time_correlate_kernel, dim3(n_delays), dim3(1024), 0, a->stream, a->d_in, a->d_tc_code, static_cast<int>(code_len), a->d_tc_delays,
+        GSH_HIP(hipMemcpyAsync(a->d_tc_code, code_iq, sizeof(float2) * code_len, hipMemcpyHostToDevice, a->stream()));
+        GSH_HIP(hipMemcpyAsync(a->d_tc_delays, delays, sizeof(uint32_t) * n_delays, hipMemcpyHostToDevice, a->stream()));
+        hipLaunchKernelGGL(time_correlate_kernel, dim3(n_delays), dim3(1024), 0, a->stream(), a->d_in, a->d_tc_code, static_cast<int>(code_len), a->d_tc_delays,
             a->h_bins_hz[doppler_index], 1.0 / static_cast<double>(a->conf.fs_in), a->d_tc_out);
         GSH_HIP(hipGetLastError());
-        GSH_HIP(hipMemcpyAsync(out_iq, a->d_tc_out, sizeof(float2) * n_delays, hipMemcpyDeviceToHost, a->stream));
-        GSH_HIP(hipStreamSynchronize(a->stream));
+        GSH_HIP(hipMemcpyAsync(out_iq, a->d_tc_out, sizeof(float2) * n_delays, hipMemcpyDeviceToHost, a->stream()));
+        GSH_HIP(hipStreamSynchronize(a->stream()));
         return GSH_OK;
     }
 
     int gsh_acq_time_dwells(gsh_acq_t* a, uint32_t n_prn, int reps, float* avg_ms)
     {
-        GSH_REQUIRE(a != nullptr && avg_ms != nullptr, "null argument");
-        GSH_REQUIRE(reps >= 1, "reps %d", reps);
-        GSH_REQUIRE(n_prn >= 1 && n_prn <= a->conf.max_prn, "n_prn %u outside 1..%u", n_prn, a->conf.max_prn);
-        if (!a->have_input) return set_error(GSH_ERR_STATE, "no input block resident: call gsh_acq_dwell[_device] once first");
-        GSH_HIP(hipSetDevice(a->device));
-        int rc = enqueue_dwell(a, n_prn, 0, 1);  // warm-up
+        int rc = check_timed(a, n_prn, reps, 1, avg_ms);
         if (rc != GSH_OK) return rc;
-        GSH_HIP(hipEventRecord(a->ev0, a->stream));
+        GSH_HIP(hipSetDevice(a->device));
+        const Batch b = whole_batch(a, n_prn, 0, 1);
+        rc = run_batch(a, b);  // warm-up
+        if (rc != GSH_OK) return rc;
+        GSH_HIP(hipEventRecord(a->ev0, a->stream()));
         for (int i = 0; i < reps; i++)
             {
-                rc = enqueue_dwell(a, n_prn, 0, 1);
+                rc = run_batch(a, b);
                 if (rc != GSH_OK) return rc;
             }
-        GSH_HIP(hipEventRecord(a->ev1, a->stream));
-        GSH_HIP(hipEventSynchronize(a->ev1));
-        float ms = 0.0f;
-        GSH_HIP(hipEventElapsedTime(&ms, a->ev0, a->ev1));
-        *avg_ms = ms / static_cast<float>(reps);
-        return GSH_OK;
+        return stop_clock(a, reps, avg_ms);
     }
 
     int gsh_acq_time_dwells_pipelined(gsh_acq_t* a, uint32_t n_prn, int reps, float* avg_ms)
     {
-        GSH_REQUIRE(a != nullptr && avg_ms != nullptr, "null argument");
-        GSH_REQUIRE(reps >= 2, "reps %d (need >= 2)", reps);
-        GSH_REQUIRE(n_prn >= 1 && n_prn <= a->conf.max_prn, "n_prn %u outside 1..%u", n_prn, a->conf.max_prn);
-        if (!a->have_input) return set_error(GSH_ERR_STATE, "no input block resident: call gsh_acq_dwell[_device] once first");
+        int rc = check_timed(a, n_prn, reps, 2, avg_ms);
+        if (rc != GSH_OK) return rc;
         if (!a->onchip) return gsh_acq_time_dwells(a, n_prn, reps, avg_ms);  // the four-step path shares one scratch buffer
         if (a->split > 0 && !a->conf.use_cfar) return gsh_acq_time_dwells(a, n_prn, reps, avg_ms);  // two batches in flight would share the stored rows
         GSH_HIP(hipSetDevice(a->device));
-        const gsh_acq_conf& c = a->conf;
-        const size_t n = c.fft_size, D = static_cast<size_t>(a->n_bins), P = c.max_prn;
         // lanes: two by default.  (GSH_ACQ_LANES: profiles/oc_cell_annotated.txt)
         static const int want_lanes = [] { const char* e = std::getenv("GSH_ACQ_LANES"); return e != nullptr ? std::min(std::max(std::atoi(e), 2), static_cast<int>(gsh_acq::MAX_LANES)) : 2; }();
-        {
-            gsh_acq::Lane& l0 = a->lane[0];
-            l0.stream = a->stream;
-            l0.d_spectra = a->d_spectra;
-            l0.d_rows = a->d_rows;
-            l0.d_subrows = a->d_subrows;
-            l0.d_waverows = a->d_waverows;
-            l0.d_z = a->d_z;
-            l0.d_results = a->d_results;
-            l0.d_arrivals = a->d_arrivals;
-        }
         while (a->n_lanes < want_lanes)
             {
-                // (every resource only where the slot does not hold one yet: a call that failed part-way -- an allocation refused -- left what it had got in the slot, and
-                //  the next call must finish that lane, not overwrite its pointers; the handle's destructor frees whatever a slot holds.  Round-5 review.)
                 gsh_acq::Lane& ln = a->lane[a->n_lanes];
                 if (ln.stream == nullptr)
                     {
                         std::vector<hipStream_t> others;
                         for (int l = 1; l < a->n_lanes; l++) others.push_back(a->lane[l].stream);
-                        const int rc2 = make_concurrent_stream(a->stream, others, &ln.stream);  // a stream on another hardware queue than the lanes so far
-                        if (rc2 != GSH_OK) return rc2;
+                        rc = make_concurrent_stream(a->stream(), others, &ln.stream);  // a stream on another hardware queue than the lanes so far
+                        if (rc != GSH_OK) return rc;
                     }
-                if (ln.d_spectra == nullptr) GSH_HIP(hipMalloc(&ln.d_spectra, sizeof(float2) * D * n));
-                if (ln.d_rows == nullptr) GSH_HIP(hipMalloc(&ln.d_rows, sizeof(gsh::RowStat) * P * D));
-                if (a->split > 0 && ln.d_subrows == nullptr) GSH_HIP(hipMalloc(&ln.d_subrows, sizeof(gsh::RowStat) * P * D * a->split));
-                if (ln.d_waverows == nullptr)
-                    GSH_HIP(hipMalloc(&ln.d_waverows, sizeof(gsh::RowStat) * P * D * static_cast<size_t>(std::max(a->split, 1)) * gsh::ONCHIP_MAX_WAVES));
-                if (a->d_z != nullptr && ln.d_z == nullptr)
-                    {
-                        GSH_HIP(hipMalloc(&ln.d_z, sizeof(float2) * P * D * n));
-                    }
-                if (ln.d_results == nullptr) GSH_HIP(hipMalloc(&ln.d_results, sizeof(gsh::DevAcqResult) * P));
-                if (ln.d_arrivals == nullptr) GSH_HIP(hipMalloc(&ln.d_arrivals, sizeof(unsigned) * P));
-                GSH_HIP(hipMemset(ln.d_arrivals, 0, sizeof(unsigned) * P));
+                rc = lane_alloc(a, ln, static_cast<size_t>(a->n_bins));
+                if (rc != GSH_OK) return rc;
                 if (ln.ev == nullptr) GSH_HIP(hipEventCreate(&ln.ev));
                 a->n_lanes++;
             }
@@ -1227,35 +1235,26 @@ extern "C"
         // 0.905 ms per 128 000-point batch against 0.82 alone).  So on the plans with non-temporal Z (pcps_onchip.hip, onchip_dit_nontemporal) only the FORWARD transforms of the next batch (41 x S work-groups, which leave
         // most of the device idle) overlap the previous batch: its cells wait for the previous batch's.  GSH_ACQ_DIT_ORDERED=0: free-running lanes, as before.
         static const bool dit_ordered = [] { const char* e = std::getenv("GSH_ACQ_DIT_ORDERED"); return e == nullptr || std::atoi(e) != 0; }();
-        const bool ordered = dit_ordered && a->d_z != nullptr && gsh::onchip_dit_nontemporal(a->split);
+        const bool ordered = dit_ordered && a->lane[0].d_z != nullptr && gsh::onchip_dit_nontemporal(a->split);
         if (ordered)
             for (int l = 0; l < lanes; l++)
                 if (a->lane[l].ev_cells == nullptr) GSH_HIP(hipEventCreateWithFlags(&a->lane[l].ev_cells, hipEventDisableTiming));
-        auto enqueue_cells = [&](const gsh_acq::Lane& ln) -> int {
-            // no_grid handles only: the batches in flight must not share the magnitude grid
-            return gsh::onchip_correlate(static_cast<int>(n), ln.d_spectra, a->d_codes, a->d_grid, ln.d_rows, ln.d_subrows, ln.d_results, ln.d_arrivals, static_cast<int>(n_prn), a->n_bins,
-                c.bit_transition_flag ? static_cast<int>(c.effective_fft_size) : 0, static_cast<int>(c.effective_fft_size), 0, 0, static_cast<int>(c.samples_per_chip), c.use_cfar, 1u, 1.0f, ln.stream,
-                ln.d_z, ln.d_waverows);
-        };
+        GSH_REQUIRE(a->conf.fold <= 1, "the pipelined timing loop does not fold");
+        Batch b = whole_batch(a, n_prn, 0, 1);
+        b.store = false;  // no_grid handles only: the batches in flight must not share the magnitude grid
+        b.weight = 1.0f;
         int last_lane = -1;
         auto enqueue = [&](int l) -> int {
-            const gsh_acq::Lane& ln = a->lane[l];
-            GSH_REQUIRE(c.fold <= 1, "the pipelined timing loop does not fold");
-            int rc = gsh::onchip_forward(static_cast<int>(n), a->d_in, 0, static_cast<int>(c.consumed_samples), 0, a->d_bins_hz,
-                static_cast<double>(c.fs_in), ln.d_spectra, a->n_bins, ln.stream);
-            if (rc != GSH_OK) return rc;
-            if (ordered && last_lane >= 0 && last_lane != l) GSH_HIP(hipStreamWaitEvent(ln.stream, a->lane[last_lane].ev_cells, 0));
-            rc = enqueue_cells(ln);
-            if (rc != GSH_OK) return rc;
-            if (ordered) GSH_HIP(hipEventRecord(ln.ev_cells, ln.stream));
+            b.lane = &a->lane[l];
+            b.cells_after = (ordered && last_lane >= 0 && last_lane != l) ? a->lane[last_lane].ev_cells : nullptr;
+            b.cells_done = ordered ? a->lane[l].ev_cells : nullptr;
             last_lane = l;
-            return GSH_OK;
+            return run_batch(a, b);
         };
-        int rc = GSH_OK;
         for (int l = 0; l < lanes && rc == GSH_OK; l++) rc = enqueue(l);  // warm-up on every lane
         if (rc != GSH_OK) return rc;
         for (int l = 0; l < lanes; l++) GSH_HIP(hipStreamSynchronize(a->lane[l].stream));
-        GSH_HIP(hipEventRecord(a->ev0, a->stream));
+        GSH_HIP(hipEventRecord(a->ev0, a->stream()));
         for (int l = 1; l < lanes; l++) GSH_HIP(hipStreamWaitEvent(a->lane[l].stream, a->ev0, 0));
         for (int i = 0; i < reps; i++)
             {
@@ -1265,14 +1264,9 @@ extern "C"
         for (int l = 1; l < lanes; l++)
             {
                 GSH_HIP(hipEventRecord(a->lane[l].ev, a->lane[l].stream));
-                GSH_HIP(hipStreamWaitEvent(a->stream, a->lane[l].ev, 0));
+                GSH_HIP(hipStreamWaitEvent(a->stream(), a->lane[l].ev, 0));
             }
-        GSH_HIP(hipEventRecord(a->ev1, a->stream));
-        GSH_HIP(hipEventSynchronize(a->ev1));
-        float ms = 0.0f;
-        GSH_HIP(hipEventElapsedTime(&ms, a->ev0, a->ev1));
-        *avg_ms = ms / static_cast<float>(reps);
-        return GSH_OK;
+        return stop_clock(a, reps, avg_ms);
     }
 
     float gsh_acq_compute_threshold(float pfa, uint32_t effective_fft_size, uint32_t num_doppler_bins, uint32_t max_dwells)
