@@ -18,7 +18,7 @@
 //     the composed map at 0.  Same result as the reference's loop for any input, including ones that saturate.
 // The phasors phi[0] = (cos r, -sin r) and inc = exp(-j s) are formed on the HOST with the C library (exactly the expressions of
 // cpu_multicorrelator_16sc.cc:89-93), because the recurrence amplifies nothing but also forgives nothing: a last-bit difference in inc is a different result.
-#include "gsh_internal.h"
+#include "bank_host.h"
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -360,19 +360,16 @@ struct gsh_bank16
     short2* d_codes{nullptr};
     int* d_code_lens{nullptr};
     std::vector<int> h_code_lens;
-    short2* d_stream_owned{nullptr};
-    size_t stream_owned_cap{0};
+    gsh::DeviceBuf<short2> stream_owned;
     const short2* d_stream{nullptr};
     unsigned long long stream_len{0};
-    gsh::Job16Dev* d_jobs{nullptr};
-    short2* d_out{nullptr};
-    int jobs_cap{0};
-    short2* d_rot{nullptr};
-    size_t rot_cap{0};  // samples
+    gsh::DeviceBuf<gsh::Job16Dev> jobs;
+    gsh::DeviceBuf<short2> out;
+    gsh::DeviceBuf<short2> rot;  // a scratch row of rot_stride samples per job
     std::vector<gsh::Job16Dev> h_jobs;
-    std::vector<short2> h_out;
     int n_jobs{0};
     int max_taps{0};
+    unsigned long long max_end{0};  // the staged batch's largest window end
     unsigned long long rot_stride{0};
     hipEvent_t ev0{nullptr}, ev1{nullptr};
 };
@@ -384,6 +381,7 @@ using gsh::set_error;
 int bank16_launch(gsh_bank16* b)
 {
     if (b->n_jobs <= 0) return GSH_OK;
+    GSH_TRY(gsh::batch_fits_stream(b->d_stream, b->max_end, 0, b->stream_len));  // the stream may have been re-attached, shorter, since the upload
     int sims = 1024;
     {
         hipDeviceProp_t prop;
@@ -397,7 +395,7 @@ int bank16_launch(gsh_bank16* b)
     while (jpw < want && jpw < 16) jpw *= 2;  // (beyond 16 the jobs' scalars no longer fit the SGPR file: more waves per SIMD instead)
     const dim3 blk(gsh::ROT_BLOCK);
 #define GSH_ROT16(JW)                                                                                                                                              \
-    hipLaunchKernelGGL((gsh::rot16_kernel<JW>), dim3(static_cast<unsigned>((b->n_jobs + JW - 1) / JW)), blk, 0, b->stream, b->d_jobs, b->n_jobs, b->d_stream, b->d_rot, \
+    hipLaunchKernelGGL((gsh::rot16_kernel<JW>), dim3(static_cast<unsigned>((b->n_jobs + JW - 1) / JW)), blk, 0, b->stream, b->jobs.p, b->n_jobs, b->d_stream, b->rot.p, \
         b->rot_stride)
     switch (jpw)
         {
@@ -411,14 +409,14 @@ int bank16_launch(gsh_bank16* b)
     const size_t lds_b = (static_cast<size_t>(b->max_code_len) + static_cast<size_t>(gsh::C16_THREADS) * gsh::C16_ROW) * sizeof(short2);
     const dim3 grid(static_cast<unsigned>(b->n_jobs)), block(gsh::C16_THREADS);
     if (b->max_taps <= 1)
-        hipLaunchKernelGGL((gsh::corr16_kernel<1>), grid, block, lds_b, b->stream, b->d_jobs, b->d_codes, b->d_code_lens, b->max_code_len, b->d_rot, b->rot_stride, b->d_out);
+        hipLaunchKernelGGL((gsh::corr16_kernel<1>), grid, block, lds_b, b->stream, b->jobs.p, b->d_codes, b->d_code_lens, b->max_code_len, b->rot.p, b->rot_stride, b->out.p);
     else if (b->max_taps <= 3)
-        hipLaunchKernelGGL((gsh::corr16_kernel<3>), grid, block, lds_b, b->stream, b->d_jobs, b->d_codes, b->d_code_lens, b->max_code_len, b->d_rot, b->rot_stride, b->d_out);
+        hipLaunchKernelGGL((gsh::corr16_kernel<3>), grid, block, lds_b, b->stream, b->jobs.p, b->d_codes, b->d_code_lens, b->max_code_len, b->rot.p, b->rot_stride, b->out.p);
     else if (b->max_taps <= 5)
-        hipLaunchKernelGGL((gsh::corr16_kernel<5>), grid, block, lds_b, b->stream, b->d_jobs, b->d_codes, b->d_code_lens, b->max_code_len, b->d_rot, b->rot_stride, b->d_out);
+        hipLaunchKernelGGL((gsh::corr16_kernel<5>), grid, block, lds_b, b->stream, b->jobs.p, b->d_codes, b->d_code_lens, b->max_code_len, b->rot.p, b->rot_stride, b->out.p);
     else
-        hipLaunchKernelGGL((gsh::corr16_kernel<GSH_MAX_TAPS>), grid, block, lds_b, b->stream, b->d_jobs, b->d_codes, b->d_code_lens, b->max_code_len, b->d_rot, b->rot_stride,
-            b->d_out);
+        hipLaunchKernelGGL((gsh::corr16_kernel<GSH_MAX_TAPS>), grid, block, lds_b, b->stream, b->jobs.p, b->d_codes, b->d_code_lens, b->max_code_len, b->rot.p, b->rot_stride,
+            b->out.p);
     GSH_HIP(hipGetLastError());
     return GSH_OK;
 }
@@ -475,10 +473,7 @@ extern "C"
         if (b->stream) (void)hipStreamSynchronize(b->stream);
         if (b->d_codes) (void)hipFree(b->d_codes);
         if (b->d_code_lens) (void)hipFree(b->d_code_lens);
-        if (b->d_stream_owned) (void)hipFree(b->d_stream_owned);
-        if (b->d_jobs) (void)hipFree(b->d_jobs);
-        if (b->d_out) (void)hipFree(b->d_out);
-        if (b->d_rot) (void)hipFree(b->d_rot);
+        (void)gsh::release_all(b->stream_owned, b->jobs, b->out, b->rot);
         if (b->ev0) (void)hipEventDestroy(b->ev0);
         if (b->ev1) (void)hipEventDestroy(b->ev1);
         if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -503,17 +498,10 @@ extern "C"
         GSH_REQUIRE(b != nullptr && (iq != nullptr || n_samples == 0), "null argument");
         GSH_HIP(hipSetDevice(b->device));
         GSH_HIP(hipStreamSynchronize(b->stream));
-        if (n_samples > b->stream_owned_cap || b->d_stream_owned == nullptr)
-            {
-                if (b->d_stream_owned) GSH_HIP(hipFree(b->d_stream_owned));
-                b->d_stream_owned = nullptr;
-                b->stream_owned_cap = 0;
-                const size_t cap = std::max<size_t>(static_cast<size_t>(n_samples), 64);  // (an empty stream is a stream: a call over zero samples answers zeros, as the reference's loop does)
-                GSH_HIP(hipMalloc(&b->d_stream_owned, sizeof(short2) * cap));
-                b->stream_owned_cap = cap;
-            }
-        if (n_samples > 0) GSH_HIP(hipMemcpy(b->d_stream_owned, iq, sizeof(short2) * static_cast<size_t>(n_samples), hipMemcpyHostToDevice));
-        b->d_stream = b->d_stream_owned;
+        // (an empty stream is a stream: a call over zero samples answers zeros, as the reference's loop does)
+        GSH_TRY(b->stream_owned.grow(std::max<size_t>(static_cast<size_t>(n_samples), 64)));
+        if (n_samples > 0) GSH_HIP(hipMemcpy(b->stream_owned.p, iq, sizeof(short2) * static_cast<size_t>(n_samples), hipMemcpyHostToDevice));
+        b->d_stream = b->stream_owned.p;
         b->stream_len = n_samples;
         return GSH_OK;
     }
@@ -534,6 +522,7 @@ extern "C"
         GSH_REQUIRE(b->d_stream != nullptr || n_jobs == 0, "no sample stream attached");
         b->n_jobs = 0;
         int max_n = 0, max_taps = 0;
+        unsigned long long max_end = 0;
         b->h_jobs.resize(static_cast<size_t>(n_jobs));
         for (int i = 0; i < n_jobs; i++)
             {
@@ -570,36 +559,23 @@ extern "C"
                 for (int t = 0; t < GSH_MAX_TAPS; t++) d.shifts[t] = t < j.n_taps ? j.shifts_chips[t] : 0.0f;
                 max_n = std::max(max_n, j.n_samples);
                 max_taps = std::max(max_taps, j.n_taps);
+                max_end = std::max(max_end, static_cast<unsigned long long>(j.sample_offset) + static_cast<unsigned long long>(j.n_samples));
             }
         if (n_jobs == 0) return GSH_OK;
         GSH_HIP(hipSetDevice(b->device));
         GSH_HIP(hipStreamSynchronize(b->stream));
-        if (n_jobs > b->jobs_cap)
-            {
-                if (b->d_jobs) GSH_HIP(hipFree(b->d_jobs));
-                if (b->d_out) GSH_HIP(hipFree(b->d_out));
-                b->d_jobs = nullptr;
-                b->d_out = nullptr;
-                b->jobs_cap = 0;
-                GSH_HIP(hipMalloc(&b->d_jobs, sizeof(gsh::Job16Dev) * static_cast<size_t>(n_jobs)));
-                GSH_HIP(hipMalloc(&b->d_out, sizeof(short2) * GSH_MAX_TAPS * static_cast<size_t>(n_jobs)));
-                b->jobs_cap = n_jobs;
-            }
+        const size_t n = static_cast<size_t>(n_jobs);
+        if (n > b->jobs.cap) GSH_TRY(gsh::release_all(b->jobs, b->out));
+        GSH_TRY(b->jobs.grow(n));
+        GSH_TRY(b->out.grow(GSH_MAX_TAPS * n));
         const unsigned long long stride = (static_cast<unsigned long long>(std::max(max_n, 1)) + 63ull) & ~63ull;
-        const size_t need = static_cast<size_t>(stride) * static_cast<size_t>(n_jobs);
-        if (need > b->rot_cap)
-            {
-                if (b->d_rot) GSH_HIP(hipFree(b->d_rot));
-                b->d_rot = nullptr;
-                b->rot_cap = 0;
-                GSH_HIP(hipMalloc(&b->d_rot, sizeof(short2) * need));
-                b->rot_cap = need;
-            }
+        GSH_TRY(b->rot.grow(static_cast<size_t>(stride) * n));
         b->rot_stride = stride;
-        GSH_HIP(hipMemcpyAsync(b->d_jobs, b->h_jobs.data(), sizeof(gsh::Job16Dev) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
+        GSH_HIP(hipMemcpyAsync(b->jobs.p, b->h_jobs.data(), sizeof(gsh::Job16Dev) * n, hipMemcpyHostToDevice, b->stream));
         GSH_HIP(hipStreamSynchronize(b->stream));
         b->n_jobs = n_jobs;
         b->max_taps = max_taps;
+        b->max_end = max_end;
         return GSH_OK;
     }
 
@@ -616,7 +592,7 @@ extern "C"
         GSH_REQUIRE(n_jobs >= 0 && n_jobs <= b->n_jobs, "n_jobs %d outside 0..%d", n_jobs, b->n_jobs);
         GSH_HIP(hipSetDevice(b->device));
         GSH_HIP(hipStreamSynchronize(b->stream));
-        if (n_jobs > 0) GSH_HIP(hipMemcpy(out_iq, b->d_out, sizeof(short2) * GSH_MAX_TAPS * static_cast<size_t>(n_jobs), hipMemcpyDeviceToHost));
+        if (n_jobs > 0) GSH_HIP(hipMemcpy(out_iq, b->out.p, sizeof(short2) * GSH_MAX_TAPS * static_cast<size_t>(n_jobs), hipMemcpyDeviceToHost));
         return GSH_OK;
     }
 
@@ -635,20 +611,8 @@ extern "C"
         GSH_REQUIRE(reps >= 1 && reps <= 100000, "reps %d outside 1..100000", reps);
         GSH_REQUIRE(b->n_jobs > 0, "no job table uploaded");
         GSH_HIP(hipSetDevice(b->device));
-        int rc = bank16_launch(b);  // warm-up
-        if (rc != GSH_OK) return rc;
-        GSH_HIP(hipEventRecord(b->ev0, b->stream));
-        for (int r = 0; r < reps; r++)
-            {
-                rc = bank16_launch(b);
-                if (rc != GSH_OK) return rc;
-            }
-        GSH_HIP(hipEventRecord(b->ev1, b->stream));
-        GSH_HIP(hipEventSynchronize(b->ev1));
-        float ms = 0.0f;
-        GSH_HIP(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-        *avg_ms = ms / static_cast<float>(reps);
-        return GSH_OK;
+        GSH_TRY(bank16_launch(b));  // warm-up
+        return gsh::time_launches(b->ev0, b->ev1, b->stream, reps, avg_ms, [b] { return bank16_launch(b); });
     }
 }
 

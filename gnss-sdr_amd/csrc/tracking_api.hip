@@ -1,6 +1,8 @@
 // C-ABI tracking entry points (include/gnss_sdr_hip.h): the batched correlator bank
 // (gsh_bank_*) and the one-to-one Cpu_Multicorrelator_Real_Codes replacement (gsh_mcorr_*)
 // built on top of it.  Host-side bookkeeping only; the arithmetic is in multicorrelator.hip.
+// Every entry is a short sequence of the file-local steps below (and of bank_host.h); each step is written once.
+#include "bank_host.h"
 #include "multicorrelator.h"
 #include "multicorrelator_wide.h"
 #include "sample_stream.h"
@@ -9,6 +11,38 @@
 #include <new>
 #include <string>
 #include <vector>
+
+namespace
+{
+// What bank_stage_jobs learns about a batch of the narrow bank.  Committed to the bank once, when the batch is staged; invalidate() whenever the staged table no
+// longer stands for what a launch may run.
+struct StagedBatch
+{
+    int n_jobs{0};
+    int max_taps{0};
+    int mode{0};
+    int min_samples{0};
+    int max_samples{0};
+    unsigned long long max_end{0};  // flat streams; 0 on a ring, where residency is checked per job
+    unsigned long long ring_min_start{0}, ring_max_end{0};  // absolute sample range of the batch (ring-bound banks)
+    // windowed code staging (multicorrelator.hip): possible when every job of the batch is mode 0 with code_step >= 0
+    bool window_eligible{false};
+    bool pair{false};  // the batch's 2- / 3-tap jobs are all mcorr_pair_eligible (multicorrelator.h)
+    bool half{false};  // ... and all mcorr_half_chip_eligible: taps at exactly -0.5 / 0 / +0.5 chip, no code of the bank too long
+    double win_step_max{0.0};       // largest code_phase_step_chips of the batch (code samples per input sample)
+    double win_code_span_max{0.0};  // largest code_phase_step_chips * n_samples of the batch: code samples one window walks
+    double win_shift_span{0.0};     // largest (max shift - min shift) of the batch
+    // pair fusion (multicorrelator.hip, AUX kernels): a single-tap job that follows a job with the same window and NCO parameters (the data
+    // prompt track_pilot adds to a pilot channel, trk.cc:1246-1256) is computed by that job's work-groups instead of a second pass
+    int n_fused{0};
+    // per-flavour launch lists (jobs grouped by tap-count class, fused partners left out); used when a batch mixes classes or has fused jobs
+    bool use_classes{false};
+    bool lists_fused{false};
+    gsh::McorrClassPlan class_plan{};
+
+    void invalidate() { *this = StagedBatch{}; }
+};
+}  // namespace
 
 struct gsh_bank
 {
@@ -20,101 +54,55 @@ struct gsh_bank
     float* d_code_images{nullptr};      // per slot, the LDS image of the half-chip flavour (multicorrelator.h mcorr_build_half_image); banks of codes short enough for it only
     int* d_code_lens{nullptr};
     std::vector<int> h_code_lens;
-    float2* d_stream_owned{nullptr};
-    size_t stream_owned_cap{0};
+    gsh::DeviceBuf<float2> stream_owned;
     const float2* d_stream{nullptr};
     unsigned long long stream_len{0};
-    gsh_corr_job* d_jobs{nullptr};
-    float2* d_out{nullptr};
-    float2* d_partials{nullptr};
-    size_t partials_cap{0};
-    int jobs_cap{0};
-    int n_jobs{0};
-    int max_taps{0};
-    int mode{0};
-    int min_samples{0};
-    unsigned long long max_end{0};
-    int splits_user{0};
-    unsigned long long sample_base{0};  // gsh_bank_set_sample_base
-    unsigned long long ring_min_start{0}, ring_max_end{0};  // absolute sample range of the staged batch (ring-bound banks)
-    // windowed code staging (multicorrelator.hip): possible when every job of the batch is mode 0 with code_step >= 0
-    bool window_eligible{false};
-    bool pair{false};                   // the staged batch's 2- / 3-tap jobs are all mcorr_pair_eligible (multicorrelator.h)
-    bool half{false};                   // ... and all mcorr_half_chip_eligible: taps at exactly -0.5 / 0 / +0.5 chip, no code of the bank too long
-    double win_step_max{0.0};   // largest code_phase_step_chips of the batch (code samples per input sample)
-    double win_code_span_max{0.0};  // largest code_phase_step_chips * n_samples of the batch: code samples one window walks
-    double win_shift_span{0.0}; // largest (max shift - min shift) of the batch
-    int max_samples{0};
-    // pair fusion (multicorrelator.hip, AUX kernels): a single-tap job that follows a job with the same window and NCO parameters (the data
-    // prompt track_pilot adds to a pilot channel, trk.cc:1246-1256) is computed by that job's work-groups instead of a second pass
-    int fusion_user{1};
-    int n_fused{0};
-    int* d_aux{nullptr};
-    int aux_cap{0};
-    std::vector<int> h_aux;
-    // per-flavour launch lists (jobs grouped by tap-count class, fused partners left out); used when a batch mixes classes or has fused jobs
-    bool use_classes{false};
-    bool lists_fused{false};
-    gsh::McorrClassPlan class_plan{};
-    int* d_list{nullptr};
-    int list_cap{0};
-    std::vector<int> h_list;
-    hipEvent_t ev0{nullptr}, ev1{nullptr};
     gsh_stream* ring{nullptr};          // when set, job windows are absolute sample indices inside this ring
-    gsh_corr_job* h_jobs{nullptr};      // pinned staging (ring translation; one-synchronisation gsh_bank_correlate)
-    float2* h_out{nullptr};             // pinned
-    int h_cap{0};
+    int splits_user{0};
+    int fusion_user{1};
+    unsigned long long sample_base{0};  // gsh_bank_set_sample_base
+    hipEvent_t ev0{nullptr}, ev1{nullptr};
+    StagedBatch batch;
+    gsh::DeviceBuf<gsh_corr_job> jobs;
+    gsh::DeviceBuf<float2> out, partials;
+    gsh::DeviceBuf<int> aux, list;
+    std::vector<int> h_aux, h_list;
+    gsh::PinnedBuf<gsh_corr_job> h_jobs;  // staging (ring translation; one-synchronisation gsh_bank_correlate)
+    gsh::PinnedBuf<float2> h_out;
     // the wide bank (gsh_bank_correlate_wide, multicorrelator_wide.hip): a job table, outputs and staging of its own -- the narrow calls' staged batch stays as it is
-    gsh_corr_job_wide* d_wjobs{nullptr};
-    float2* d_wout{nullptr};
-    float2* d_wpartials{nullptr};
-    size_t wpartials_cap{0};
-    int wjobs_cap{0};
-    gsh_corr_job_wide* h_wjobs{nullptr};  // pinned
-    float2* h_wout{nullptr};              // pinned
+    gsh::DeviceBuf<gsh_corr_job_wide> wjobs;
+    gsh::DeviceBuf<float2> wout, wpartials;
+    gsh::PinnedBuf<gsh_corr_job_wide> h_wjobs;
+    gsh::PinnedBuf<float2> h_wout;
 };
 
 namespace
 {
+using gsh::release_all;
 using gsh::set_error;
-
-int bank_reserve_jobs(gsh_bank* b, int n)
-{
-    if (n <= b->jobs_cap) return GSH_OK;
-    if (b->d_jobs) GSH_HIP(hipFree(b->d_jobs));
-    if (b->d_out) GSH_HIP(hipFree(b->d_out));
-    b->d_jobs = nullptr;
-    b->d_out = nullptr;
-    b->jobs_cap = 0;
-    GSH_HIP(hipMalloc(&b->d_jobs, sizeof(gsh_corr_job) * static_cast<size_t>(n)));
-    GSH_HIP(hipMalloc(&b->d_out, sizeof(float2) * GSH_MAX_TAPS * static_cast<size_t>(n)));
-    b->jobs_cap = n;
-    return GSH_OK;
-}
 
 int validate_job(const gsh_bank* b, const gsh_corr_job& j, int idx);
 
-int bank_reserve_staging(gsh_bank* b, int n)
+// the position in the bank's ring of job idx's window [start, start + n_samples) (windows never wrap: the ring mirrors its head)
+int ring_position(const gsh_bank* b, int idx, unsigned long long start, int n_samples, uint64_t* pos)
 {
-    if (n <= b->h_cap) return GSH_OK;
-    if (b->h_jobs) GSH_HIP(hipHostFree(b->h_jobs));
-    if (b->h_out) GSH_HIP(hipHostFree(b->h_out));
-    b->h_jobs = nullptr;
-    b->h_out = nullptr;
-    b->h_cap = 0;
-    const int cap = std::max(n, 64);
-    GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_jobs), sizeof(gsh_corr_job) * static_cast<size_t>(cap), hipHostMallocDefault));
-    GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_out), sizeof(float2) * GSH_MAX_TAPS * static_cast<size_t>(cap), hipHostMallocDefault));
-    b->h_cap = cap;
+    const float2* w = nullptr;
+    const int rc = gsh::stream_window(b->ring, start, static_cast<unsigned long long>(n_samples), &w);
+    if (rc != GSH_OK)
+        {
+            const std::string why = gsh_last_error();
+            return set_error(rc, "job %d: %s", idx, why.c_str());
+        }
+    *pos = static_cast<uint64_t>(w - b->ring->d_ring);
     return GSH_OK;
 }
 
 // launch classes: a 3-tap job inside a 5-tap launch would pay for five taps, so a batch that mixes tap counts is launched per kernel flavour;
 // with_fusion leaves the fused partners out (their leaders write their rows).  Reads the staged copy of the batch (h_jobs, h_aux).
-int bank_build_lists(gsh_bank* b, bool with_fusion)
+int bank_build_lists(gsh_bank* b, StagedBatch& s, bool with_fusion)
 {
-    const int n_jobs = b->n_jobs;
-    const gsh_corr_job* jobs = b->h_jobs;
+    const int n_jobs = s.n_jobs;
+    const gsh_corr_job* jobs = b->h_jobs.p;
     int count[4] = {0, 0, 0, 0};
     bool has_aux[4] = {false, false, false, false};
     auto cls_of = [](int taps) { return taps <= 1 ? 0 : (taps <= 3 ? 1 : (taps <= 5 ? 2 : 3)); };
@@ -126,9 +114,9 @@ int bank_build_lists(gsh_bank* b, bool with_fusion)
             if (with_fusion && b->h_aux[i] >= 0) has_aux[c] = true;
         }
     const int classes = (count[0] > 0) + (count[1] > 0) + (count[2] > 0) + (count[3] > 0);
-    b->use_classes = (classes > 1) || with_fusion;
-    b->lists_fused = with_fusion;
-    if (!b->use_classes) return GSH_OK;
+    s.use_classes = (classes > 1) || with_fusion;
+    s.lists_fused = with_fusion;
+    if (!s.use_classes) return GSH_OK;
     int off[4];
     off[0] = 0;
     for (int c = 1; c < 4; c++) off[c] = off[c - 1] + count[c - 1];
@@ -139,137 +127,122 @@ int bank_build_lists(gsh_bank* b, bool with_fusion)
             if (with_fusion && b->h_aux[i] == -2) continue;
             b->h_list[static_cast<size_t>(fill[cls_of(jobs[i].n_taps)]++)] = i;
         }
-    if (b->list_cap < n_jobs)
-        {
-            if (b->d_list) GSH_HIP(hipFree(b->d_list));
-            b->d_list = nullptr;
-            b->list_cap = 0;
-            GSH_HIP(hipMalloc(&b->d_list, sizeof(int) * static_cast<size_t>(n_jobs)));
-            b->list_cap = n_jobs;
-        }
-    GSH_HIP(hipMemcpyAsync(b->d_list, b->h_list.data(), sizeof(int) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
-    b->class_plan.list = b->d_list;
+    GSH_TRY(b->list.grow(static_cast<size_t>(n_jobs)));
+    GSH_HIP(hipMemcpyAsync(b->list.p, b->h_list.data(), sizeof(int) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
+    s.class_plan.list = b->list.p;
     for (int c = 0; c < 4; c++)
         {
-            b->class_plan.offset[c] = off[c];
-            b->class_plan.count[c] = count[c];
-            b->class_plan.aux[c] = has_aux[c];
+            s.class_plan.offset[c] = off[c];
+            s.class_plan.count[c] = count[c];
+            s.class_plan.aux[c] = has_aux[c];
         }
     return GSH_OK;
 }
 
-// validate the batch, stage it in pinned memory (ring mode: absolute sample indices -> ring positions) and queue the
-// host-to-device copy on the bank's stream.  No synchronisation.
-int bank_stage_jobs(gsh_bank* b, const gsh_corr_job* jobs, int n_jobs)
+// staging, part 1: validate the jobs and derive the batch's facts.  No HIP call, nothing of the bank changes.
+int batch_facts(const gsh_bank* b, const gsh_corr_job* jobs, int n_jobs, StagedBatch& s)
 {
-    int max_taps = 0, mode = jobs[0].high_dyn, min_samples = jobs[0].n_samples, max_samples = 0;
-    unsigned long long max_end = 0;
-    bool window_eligible = (mode == 0);
-    bool pair = true;  // every job the 3-tap launch will see may read its early tap next to the late one (multicorrelator.h mcorr_pair_eligible)
-    bool half = true;  // ... and take all three taps from the prompt's index chain (mcorr_half_chip_eligible)
-    double step_max = 0.0, shift_span = 0.0, code_span = 0.0;
+    s.n_jobs = n_jobs;
+    s.mode = jobs[0].high_dyn;
+    s.min_samples = jobs[0].n_samples;
+    s.window_eligible = (s.mode == 0);
+    s.pair = true;      // every job the 3-tap launch will see may read its early tap next to the late one (multicorrelator.h mcorr_pair_eligible)
+    bool half = true;   // ... and take all three taps from the prompt's index chain (mcorr_half_chip_eligible)
+    unsigned long long min_start = ~0ull;
     for (int i = 0; i < n_jobs; i++)
         {
-            int rc = validate_job(b, jobs[i], i);
-            if (rc != GSH_OK) return rc;
-            if ((jobs[i].n_taps == 2 || jobs[i].n_taps == 3) && !gsh::mcorr_pair_eligible(jobs[i].n_taps, jobs[i].shifts_chips, jobs[i].code_phase_step_chips, jobs[i].high_dyn))
-                pair = false;
-            if ((jobs[i].n_taps == 2 || jobs[i].n_taps == 3)
-                && !gsh::mcorr_half_chip_eligible(jobs[i].n_taps, jobs[i].shifts_chips, jobs[i].code_phase_step_chips, jobs[i].high_dyn, b->max_code_len))
+            const gsh_corr_job& j = jobs[i];
+            GSH_TRY(validate_job(b, j, i));
+            if ((j.n_taps == 2 || j.n_taps == 3) && !gsh::mcorr_pair_eligible(j.n_taps, j.shifts_chips, j.code_phase_step_chips, j.high_dyn)) s.pair = false;
+            if ((j.n_taps == 2 || j.n_taps == 3) && !gsh::mcorr_half_chip_eligible(j.n_taps, j.shifts_chips, j.code_phase_step_chips, j.high_dyn, b->max_code_len))
                 half = false;
-            max_samples = std::max(max_samples, jobs[i].n_samples);
-            if (!(jobs[i].code_phase_step_chips >= 0.0f)) window_eligible = false;
-            step_max = std::max(step_max, static_cast<double>(jobs[i].code_phase_step_chips));
-            code_span = std::max(code_span, static_cast<double>(jobs[i].code_phase_step_chips) * static_cast<double>(jobs[i].n_samples));
-            float smin = jobs[i].shifts_chips[0], smax = jobs[i].shifts_chips[0];
-            for (int t = 1; t < jobs[i].n_taps; t++)
+            s.max_samples = std::max(s.max_samples, j.n_samples);
+            if (!(j.code_phase_step_chips >= 0.0f)) s.window_eligible = false;
+            s.win_step_max = std::max(s.win_step_max, static_cast<double>(j.code_phase_step_chips));
+            s.win_code_span_max = std::max(s.win_code_span_max, static_cast<double>(j.code_phase_step_chips) * static_cast<double>(j.n_samples));
+            float smin = j.shifts_chips[0], smax = j.shifts_chips[0];
+            for (int t = 1; t < j.n_taps; t++)
                 {
-                    smin = std::min(smin, jobs[i].shifts_chips[t]);
-                    smax = std::max(smax, jobs[i].shifts_chips[t]);
+                    smin = std::min(smin, j.shifts_chips[t]);
+                    smax = std::max(smax, j.shifts_chips[t]);
                 }
-            shift_span = std::max(shift_span, static_cast<double>(smax) - static_cast<double>(smin));
-            if (jobs[i].high_dyn != mode)
-                return set_error(GSH_ERR_UNSUPPORTED, "job %d: all jobs of one batch must share high_dyn (%d vs %d); split the batch", i, jobs[i].high_dyn, mode);
-            max_taps = std::max(max_taps, jobs[i].n_taps);
-            min_samples = std::min(min_samples, jobs[i].n_samples);
-            max_end = std::max(max_end, static_cast<unsigned long long>(jobs[i].sample_offset) + static_cast<unsigned long long>(jobs[i].n_samples));
+            s.win_shift_span = std::max(s.win_shift_span, static_cast<double>(smax) - static_cast<double>(smin));
+            if (j.high_dyn != s.mode)
+                return set_error(GSH_ERR_UNSUPPORTED, "job %d: all jobs of one batch must share high_dyn (%d vs %d); split the batch", i, j.high_dyn, s.mode);
+            s.max_taps = std::max(s.max_taps, j.n_taps);
+            s.min_samples = std::min(s.min_samples, j.n_samples);
+            min_start = std::min<unsigned long long>(min_start, j.sample_offset);
+            s.max_end = std::max(s.max_end, static_cast<unsigned long long>(j.sample_offset) + static_cast<unsigned long long>(j.n_samples));
         }
-    GSH_HIP(hipSetDevice(b->device));
-    int rc = bank_reserve_jobs(b, n_jobs);
-    if (rc == GSH_OK) rc = bank_reserve_staging(b, n_jobs);
-    if (rc != GSH_OK) return rc;
-    std::memcpy(b->h_jobs, jobs, sizeof(gsh_corr_job) * static_cast<size_t>(n_jobs));
+    s.half = s.pair && half;
     if (b->ring != nullptr)
         {
-            unsigned long long lo = ~0ull;
-            for (int i = 0; i < n_jobs; i++) lo = std::min<unsigned long long>(lo, jobs[i].sample_offset);
-            b->ring_min_start = n_jobs > 0 ? lo : 0ull;
-            b->ring_max_end = max_end;
-            for (int i = 0; i < n_jobs; i++)
-                {
-                    const float2* w = nullptr;
-                    rc = gsh::stream_window(b->ring, jobs[i].sample_offset, static_cast<unsigned long long>(jobs[i].n_samples), &w);
-                    if (rc != GSH_OK) return rc;
-                    b->h_jobs[i].sample_offset = static_cast<uint64_t>(w - b->ring->d_ring);
-                }
+            s.ring_min_start = min_start;
+            s.ring_max_end = s.max_end;
+            s.max_end = 0;  // residency is checked per job (bank_stage_table)
+        }
+    return GSH_OK;
+}
+
+// staging, part 2: the job table into pinned memory (ring mode: absolute sample indices -> ring positions) and from there to the device, queued on the bank's stream
+int bank_stage_table(gsh_bank* b, const gsh_corr_job* jobs, int n_jobs)
+{
+    const size_t n = static_cast<size_t>(n_jobs), staged = static_cast<size_t>(std::max(n_jobs, 64));
+    if (n > b->jobs.cap) GSH_TRY(release_all(b->jobs, b->out));
+    GSH_TRY(b->jobs.grow(n));
+    GSH_TRY(b->out.grow(GSH_MAX_TAPS * n));
+    if (staged > b->h_jobs.cap) GSH_TRY(release_all(b->h_jobs, b->h_out));
+    GSH_TRY(b->h_jobs.grow(staged));
+    GSH_TRY(b->h_out.grow(GSH_MAX_TAPS * staged));
+    std::memcpy(b->h_jobs.p, jobs, sizeof(gsh_corr_job) * n);
+    if (b->ring != nullptr)
+        {
+            for (int i = 0; i < n_jobs; i++) GSH_TRY(ring_position(b, i, jobs[i].sample_offset, jobs[i].n_samples, &b->h_jobs.p[i].sample_offset));
             b->d_stream = b->ring->d_ring;
             b->stream_len = b->ring->capacity + b->ring->max_window;
-            max_end = 0;  // residency was checked per job
         }
-    GSH_HIP(hipMemcpyAsync(b->d_jobs, b->h_jobs, sizeof(gsh_corr_job) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
-    // ---- pair fusion: job i + 1 rides on job i when it is a single tap over exactly the same samples with exactly the same NCO parameters
-    b->n_fused = 0;
-    if (b->fusion_user && mode == 0 && max_taps >= 2 && max_taps <= 5)
+    GSH_HIP(hipMemcpyAsync(b->jobs.p, b->h_jobs.p, sizeof(gsh_corr_job) * n, hipMemcpyHostToDevice, b->stream));
+    return GSH_OK;
+}
+
+// staging, part 3, pair fusion: job i + 1 rides on job i when it is a single tap over exactly the same samples with exactly the same NCO parameters
+int bank_pair_fusion(gsh_bank* b, const gsh_corr_job* jobs, StagedBatch& s)
+{
+    if (!b->fusion_user || s.mode != 0 || s.max_taps < 2 || s.max_taps > 5) return GSH_OK;
+    const int n_jobs = s.n_jobs;
+    b->h_aux.assign(static_cast<size_t>(n_jobs), -1);
+    for (int i = 0; i + 1 < n_jobs; i++)
         {
-            b->h_aux.assign(static_cast<size_t>(n_jobs), -1);
-            for (int i = 0; i + 1 < n_jobs; i++)
-                {
-                    const gsh_corr_job &p = jobs[i], &q = jobs[i + 1];
-                    if (p.n_taps < 2 || q.n_taps != 1 || b->h_aux[i] == -2) continue;
-                    if (p.sample_offset != q.sample_offset || p.n_samples != q.n_samples) continue;
-                    if (std::memcmp(&p.rem_carr_phase_rad, &q.rem_carr_phase_rad, sizeof(float)) != 0 || std::memcmp(&p.phase_step_rad, &q.phase_step_rad, sizeof(float)) != 0 ||
-                        std::memcmp(&p.rem_code_phase_chips, &q.rem_code_phase_chips, sizeof(float)) != 0 ||
-                        std::memcmp(&p.code_phase_step_chips, &q.code_phase_step_chips, sizeof(float)) != 0)
-                        continue;
-                    b->h_aux[i] = i + 1;
-                    b->h_aux[i + 1] = -2;
-                    b->n_fused++;
-                    i++;
-                }
-            if (b->n_fused > 0)
-                {
-                    if (b->aux_cap < n_jobs)
-                        {
-                            if (b->d_aux) GSH_HIP(hipFree(b->d_aux));
-                            b->d_aux = nullptr;
-                            b->aux_cap = 0;
-                            GSH_HIP(hipMalloc(&b->d_aux, sizeof(int) * static_cast<size_t>(n_jobs)));
-                            b->aux_cap = n_jobs;
-                        }
-                    GSH_HIP(hipMemcpyAsync(b->d_aux, b->h_aux.data(), sizeof(int) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
-                }
+            const gsh_corr_job &p = jobs[i], &q = jobs[i + 1];
+            if (p.n_taps < 2 || q.n_taps != 1 || b->h_aux[i] == -2) continue;
+            if (p.sample_offset != q.sample_offset || p.n_samples != q.n_samples) continue;
+            if (std::memcmp(&p.rem_carr_phase_rad, &q.rem_carr_phase_rad, sizeof(float)) != 0 || std::memcmp(&p.phase_step_rad, &q.phase_step_rad, sizeof(float)) != 0 ||
+                std::memcmp(&p.rem_code_phase_chips, &q.rem_code_phase_chips, sizeof(float)) != 0 ||
+                std::memcmp(&p.code_phase_step_chips, &q.code_phase_step_chips, sizeof(float)) != 0)
+                continue;
+            b->h_aux[i] = i + 1;
+            b->h_aux[i + 1] = -2;
+            s.n_fused++;
+            i++;
         }
-    b->n_jobs = n_jobs;
-    {
-        int rc2 = bank_build_lists(b, b->n_fused > 0);
-        if (rc2 != GSH_OK)
-            {
-                b->n_jobs = 0;
-                return rc2;
-            }
-    }
-    b->n_jobs = n_jobs;
-    b->max_taps = max_taps;
-    b->mode = mode;
-    b->min_samples = min_samples;
-    b->max_end = max_end;
-    b->max_samples = max_samples;
-    b->window_eligible = window_eligible;
-    b->pair = pair;
-    b->half = pair && half;
-    b->win_step_max = step_max;
-    b->win_code_span_max = code_span;
-    b->win_shift_span = shift_span;
+    if (s.n_fused == 0) return GSH_OK;
+    GSH_TRY(b->aux.grow(static_cast<size_t>(n_jobs)));
+    GSH_HIP(hipMemcpyAsync(b->aux.p, b->h_aux.data(), sizeof(int) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
+    return GSH_OK;
+}
+
+// validate a batch, stage it and queue its host-to-device copies on the bank's stream; the bank's staged batch is the new one on success and none on
+// failure.  No synchronisation.
+int bank_stage_jobs(gsh_bank* b, const gsh_corr_job* jobs, int n_jobs)
+{
+    b->batch.invalidate();
+    StagedBatch s;
+    GSH_TRY(batch_facts(b, jobs, n_jobs, s));
+    GSH_HIP(hipSetDevice(b->device));
+    GSH_TRY(bank_stage_table(b, jobs, n_jobs));
+    GSH_TRY(bank_pair_fusion(b, jobs, s));
+    GSH_TRY(bank_build_lists(b, s, s.n_fused > 0));
+    b->batch = s;
     return GSH_OK;
 }
 
@@ -280,14 +253,14 @@ int bank_splits(const gsh_bank* b)
         {
             // throughput mode once there are a few work-groups per CU; otherwise spread each
             // epoch over several CUs (latency mode for closed-loop tracking)
-            s = (b->n_jobs >= 1024) ? 1 : (2048 + b->n_jobs - 1) / std::max(b->n_jobs, 1);
+            s = (b->batch.n_jobs >= 1024) ? 1 : (2048 + b->batch.n_jobs - 1) / std::max(b->batch.n_jobs, 1);
         }
-    const int by_len = std::max(1, b->min_samples / 2048);  // keep >= 2048 samples per work-group
-    if (b->splits_user <= 0 && b->window_eligible && static_cast<size_t>(b->max_code_len) * sizeof(float) > 20 * 1024)
+    const int by_len = std::max(1, b->batch.min_samples / 2048);  // keep >= 2048 samples per work-group
+    if (b->splits_user <= 0 && b->batch.window_eligible && static_cast<size_t>(b->max_code_len) * sizeof(float) > 20 * 1024)
         {
             // long codes (Galileo E1 / E5, GPS L5 / L2C): the whole code in LDS leaves room for 3-4 work-groups per compute unit.  Cut the
             // windows so that a work-group only walks ~2000 code samples and stages just those (bank_window_floats).
-            const int want = static_cast<int>(std::ceil(b->win_code_span_max / 2000.0));
+            const int want = static_cast<int>(std::ceil(b->batch.win_code_span_max / 2000.0));
             s = std::max(s, std::min(want, 16));
         }
     s = std::min(s, by_len);
@@ -299,18 +272,18 @@ int bank_splits(const gsh_bank* b)
 // (batch not eligible, or the window would not be clearly smaller than the code)
 int bank_window_floats(const gsh_bank* b, int splits)
 {
-    if (!b->window_eligible) return 0;
+    if (!b->batch.window_eligible) return 0;
     // hi - lo + 1 <= step * (seg - 1) + (smax - smin) + 2 in exact arithmetic, seg the job's own segment length; the float evaluation on
     // the device moves either end by a few ulps of values below 2^24, far less than the slack added here (the kernel re-checks and
     // reports NaN if this were ever short)
     double walk = 0.0;
-    for (int i = 0; i < b->n_jobs; i++)
+    for (int i = 0; i < b->batch.n_jobs; i++)
         {
-            int seg = (b->h_jobs[i].n_samples + splits - 1) / splits;
+            int seg = (b->h_jobs.p[i].n_samples + splits - 1) / splits;
             seg = (seg + 1) & ~1;
-            walk = std::max(walk, static_cast<double>(b->h_jobs[i].code_phase_step_chips) * static_cast<double>(seg));
+            walk = std::max(walk, static_cast<double>(b->h_jobs.p[i].code_phase_step_chips) * static_cast<double>(seg));
         }
-    const double need = walk + b->win_shift_span + 16.0;
+    const double need = walk + b->batch.win_shift_span + 16.0;
     if (!(need < 1.0e6)) return 0;
     const int w = (static_cast<int>(std::ceil(need)) + 3) & ~3;
     const int full = b->max_code_len + 2 * 32;
@@ -398,8 +371,7 @@ int bank_stage_wide(gsh_bank* b, const gsh_corr_job_wide* jobs, int n_jobs, Wide
     bool whole_code = false;
     for (int i = 0; i < n_jobs; i++)
         {
-            int rc = validate_job_wide(b, jobs[i], i);
-            if (rc != GSH_OK) return rc;
+            GSH_TRY(validate_job_wide(b, jobs[i], i));
             const unsigned long long start = static_cast<unsigned long long>(jobs[i].sample_offset) + b->sample_base;
             const unsigned long long end = start + static_cast<unsigned long long>(jobs[i].n_samples);
             if (start < b->sample_base || end < start) return set_error(GSH_ERR_INVALID, "job %d: sample_offset %llu", i, static_cast<unsigned long long>(jobs[i].sample_offset));
@@ -421,56 +393,24 @@ int bank_stage_wide(gsh_bank* b, const gsh_corr_job_wide* jobs, int n_jobs, Wide
     plan->table_floats = std::min(plan->table_floats, cap);
     GSH_REQUIRE(!whole_code || b->max_code_len <= cap, "a code of %d samples does not fit the wide bank's table (%d)", b->max_code_len, cap);
     GSH_HIP(hipSetDevice(b->device));
-    if (n_jobs > b->wjobs_cap)
-        {
-            if (b->d_wjobs) GSH_HIP(hipFree(b->d_wjobs));
-            if (b->d_wout) GSH_HIP(hipFree(b->d_wout));
-            if (b->h_wjobs) GSH_HIP(hipHostFree(b->h_wjobs));
-            if (b->h_wout) GSH_HIP(hipHostFree(b->h_wout));
-            b->d_wjobs = nullptr;
-            b->d_wout = nullptr;
-            b->h_wjobs = nullptr;
-            b->h_wout = nullptr;
-            b->wjobs_cap = 0;
-            const size_t n = static_cast<size_t>(std::max(n_jobs, 32));
-            GSH_HIP(hipMalloc(&b->d_wjobs, sizeof(gsh_corr_job_wide) * n));
-            GSH_HIP(hipMalloc(&b->d_wout, sizeof(float2) * GSH_MAX_WIDE_TAPS * n));
-            GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_wjobs), sizeof(gsh_corr_job_wide) * n, hipHostMallocDefault));
-            GSH_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_wout), sizeof(float2) * GSH_MAX_WIDE_TAPS * n, hipHostMallocDefault));
-            b->wjobs_cap = static_cast<int>(n);
-        }
-    if (plan->max_splits > 1)
-        {
-            const size_t need = static_cast<size_t>(n_jobs) * plan->max_splits * GSH_MAX_WIDE_TAPS;
-            if (need > b->wpartials_cap)
-                {
-                    if (b->d_wpartials) GSH_HIP(hipFree(b->d_wpartials));
-                    b->d_wpartials = nullptr;
-                    b->wpartials_cap = 0;
-                    GSH_HIP(hipMalloc(&b->d_wpartials, sizeof(float2) * need));
-                    b->wpartials_cap = need;
-                }
-        }
-    std::memcpy(b->h_wjobs, jobs, sizeof(gsh_corr_job_wide) * static_cast<size_t>(n_jobs));
+    const size_t n = static_cast<size_t>(std::max(n_jobs, 32));
+    if (n > b->wjobs.cap) GSH_TRY(release_all(b->wjobs, b->wout, b->h_wjobs, b->h_wout));
+    GSH_TRY(b->wjobs.grow(n));
+    GSH_TRY(b->wout.grow(GSH_MAX_WIDE_TAPS * n));
+    GSH_TRY(b->h_wjobs.grow(n));
+    GSH_TRY(b->h_wout.grow(GSH_MAX_WIDE_TAPS * n));
+    if (plan->max_splits > 1) GSH_TRY(b->wpartials.grow(static_cast<size_t>(n_jobs) * plan->max_splits * GSH_MAX_WIDE_TAPS));
+    std::memcpy(b->h_wjobs.p, jobs, sizeof(gsh_corr_job_wide) * static_cast<size_t>(n_jobs));
     for (int i = 0; i < n_jobs; i++)
         {
             const unsigned long long start = static_cast<unsigned long long>(jobs[i].sample_offset) + b->sample_base;
             if (b->ring != nullptr)
-                {
-                    const float2* w = nullptr;
-                    int rc = gsh::stream_window(b->ring, start, static_cast<unsigned long long>(jobs[i].n_samples), &w);
-                    if (rc != GSH_OK)
-                        {
-                            const std::string why = gsh_last_error();
-                            return set_error(rc, "job %d: %s", i, why.c_str());
-                        }
-                    b->h_wjobs[i].sample_offset = static_cast<uint64_t>(w - b->ring->d_ring);
-                }
+                GSH_TRY(ring_position(b, i, start, jobs[i].n_samples, &b->h_wjobs.p[i].sample_offset));
             else
-                b->h_wjobs[i].sample_offset = start;
+                b->h_wjobs.p[i].sample_offset = start;
         }
     if (b->ring != nullptr) b->d_stream = b->ring->d_ring;
-    GSH_HIP(hipMemcpyAsync(b->d_wjobs, b->h_wjobs, sizeof(gsh_corr_job_wide) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
+    GSH_HIP(hipMemcpyAsync(b->wjobs.p, b->h_wjobs.p, sizeof(gsh_corr_job_wide) * static_cast<size_t>(n_jobs), hipMemcpyHostToDevice, b->stream));
     return GSH_OK;
 }
 
@@ -478,26 +418,95 @@ int bank_launch_wide(gsh_bank* b, int n_jobs, const WidePlan& plan)
 {
     gsh::McorrWideArgs a{};
     a.stream = b->d_stream;
-    a.jobs = b->d_wjobs;
+    a.jobs = b->wjobs.p;
     a.codes = b->d_codes;
     a.code_lens = b->d_code_lens;
     a.code_stride = b->max_code_len;
-    a.out = b->d_wout;
-    a.partials = b->d_wpartials;
+    a.out = b->wout.p;
+    a.partials = b->wpartials.p;
     a.n_jobs = n_jobs;
     a.splits_user = b->splits_user;
     a.max_splits = plan.max_splits;
     a.table_floats = plan.table_floats;
     a.max_taps = plan.max_taps;
-    if (b->ring != nullptr)
-        {
-            int rc = gsh::stream_wait_pushed(b->ring, plan.max_end, b->stream);  // the push that completed this batch's newest window
-            if (rc != GSH_OK) return rc;
-        }
-    int rc = gsh::mcorr_wide_launch(a, b->stream);
-    if (rc != GSH_OK) return rc;
+    if (b->ring != nullptr) GSH_TRY(gsh::stream_wait_pushed(b->ring, plan.max_end, b->stream));  // the push that completed this batch's newest window
+    GSH_TRY(gsh::mcorr_wide_launch(a, b->stream));
     if (b->ring != nullptr) return gsh::stream_mark_read(b->ring, plan.min_start, b->stream);  // pushes that would overwrite these windows wait
     return GSH_OK;
+}
+
+// ---- the steps of a narrow launch
+// may the staged batch run on what is attached now?  (Both may have changed since it was staged: set_stream_*, set_sample_base, pushes.)
+int bank_may_launch(const gsh_bank* b)
+{
+    const StagedBatch& s = b->batch;
+    if (b->ring == nullptr) return gsh::batch_fits_stream(b->d_stream, s.max_end, b->sample_base, b->stream_len);
+    if (s.ring_max_end == 0) return GSH_OK;
+    // the shifted windows must be resident and pushed: a base that points at samples the ring no longer (or not yet) holds would make
+    // the kernel read whatever lives at those ring positions now
+    const unsigned long long lo = s.ring_min_start + b->sample_base, hi = s.ring_max_end + b->sample_base;
+    if (lo < gsh::stream_oldest(b->ring) || hi > b->ring->next)
+        return set_error(GSH_ERR_INVALID, "windows [%llu, %llu) (sample_base %llu) are not resident (ring holds [%llu, %llu))", lo, hi, b->sample_base,
+            gsh::stream_oldest(b->ring), static_cast<unsigned long long>(b->ring->next));
+    return GSH_OK;
+}
+
+// what the launcher is told about the staged batch cut `splits` ways; aux is set when the batch's fused pairs run fused
+gsh::McorrArgs bank_launch_args(const gsh_bank* b, int splits)
+{
+    gsh::McorrArgs a;
+    a.stream = b->d_stream;
+    a.stream_len = b->stream_len;
+    a.jobs = b->jobs.p;
+    a.codes = b->d_codes;
+    a.code_lens = b->d_code_lens;
+    a.code_stride = b->max_code_len;
+    a.code_images = b->d_code_images;
+    a.out = b->out.p;
+    a.partials = b->partials.p;
+    a.n_jobs = b->batch.n_jobs;
+    a.splits = splits;
+    a.window_floats = bank_window_floats(b, splits);
+    a.packed = gsh::mcorr_packed_default();
+    a.fac = gsh::mcorr_fac_default();
+    a.pair = b->batch.pair ? 1 : 0;
+    a.half = b->batch.half ? 1 : 0;
+    a.sample_base = b->sample_base;
+    a.ring_capacity = b->ring != nullptr ? b->ring->capacity : 0ull;
+    // the second code table must not cost the occupancy the fusion is meant to win: only with windowed tables or short codes
+    const bool fuse = b->batch.n_fused > 0 && (a.window_floats > 0 || static_cast<size_t>(b->max_code_len) * sizeof(float) <= 10 * 1024);
+    a.aux = fuse ? b->aux.p : nullptr;
+    a.job_list = nullptr;
+    a.n_launch = b->batch.n_jobs;
+    return a;
+}
+
+// ---- the tail of every synchronous entry.  `rc` is what staging and launch answered: a failure waits for whatever was queued (and leaves no staged batch
+// where the narrow table was touched); a success brings bytes_d2h bytes from `d_from` through `pinned` and hands the first bytes_out of them to the caller.
+int bank_fetch(gsh_bank* b, int rc, bool narrow, const float2* d_from, float2* pinned, size_t bytes_d2h, void* out, size_t bytes_out)
+{
+    if (rc != GSH_OK)
+        {
+            (void)hipStreamSynchronize(b->stream);
+            if (narrow) b->batch.invalidate();
+            return rc;
+        }
+    GSH_HIP(hipMemcpyAsync(pinned, d_from, bytes_d2h, hipMemcpyDeviceToHost, b->stream));
+    GSH_HIP(hipStreamSynchronize(b->stream));
+    std::memcpy(out, pinned, bytes_out);
+    return GSH_OK;
+}
+
+int bank_run_wide(gsh_bank* b, const gsh_corr_job_wide* jobs, int n_jobs, WidePlan* plan)
+{
+    GSH_TRY(bank_stage_wide(b, jobs, n_jobs, plan));
+    return bank_launch_wide(b, n_jobs, *plan);
+}
+
+int bank_run(gsh_bank* b, const gsh_corr_job* jobs, int n_jobs)
+{
+    GSH_TRY(bank_stage_jobs(b, jobs, n_jobs));
+    return gsh_bank_launch(b, nullptr);
 }
 }  // namespace
 
@@ -548,21 +557,10 @@ extern "C"
         if (b->d_codes) (void)hipFree(b->d_codes);
         if (b->d_code_images) (void)hipFree(b->d_code_images);
         if (b->d_code_lens) (void)hipFree(b->d_code_lens);
-        if (b->d_stream_owned) (void)hipFree(b->d_stream_owned);
-        if (b->d_jobs) (void)hipFree(b->d_jobs);
-        if (b->d_out) (void)hipFree(b->d_out);
-        if (b->d_partials) (void)hipFree(b->d_partials);
-        if (b->d_aux) (void)hipFree(b->d_aux);
-        if (b->d_list) (void)hipFree(b->d_list);
+        (void)release_all(b->stream_owned, b->jobs, b->out, b->partials, b->aux, b->list);
         if (b->ev0) (void)hipEventDestroy(b->ev0);
         if (b->ev1) (void)hipEventDestroy(b->ev1);
-        if (b->h_jobs) (void)hipHostFree(b->h_jobs);
-        if (b->h_out) (void)hipHostFree(b->h_out);
-        if (b->d_wjobs) (void)hipFree(b->d_wjobs);
-        if (b->d_wout) (void)hipFree(b->d_wout);
-        if (b->d_wpartials) (void)hipFree(b->d_wpartials);
-        if (b->h_wjobs) (void)hipHostFree(b->h_wjobs);
-        if (b->h_wout) (void)hipHostFree(b->h_wout);
+        (void)release_all(b->h_jobs, b->h_out, b->wjobs, b->wout, b->wpartials, b->h_wjobs, b->h_wout);
         if (b->stream) (void)hipStreamDestroy(b->stream);
         delete b;
     }
@@ -593,18 +591,10 @@ extern "C"
         GSH_REQUIRE(n_samples >= 1, "empty stream");
         GSH_HIP(hipSetDevice(b->device));
         GSH_HIP(hipStreamSynchronize(b->stream));
-        const size_t need = static_cast<size_t>(n_samples) + 2;  // one spare pair: 16-byte loads may touch sample n
-        if (need > b->stream_owned_cap)
-            {
-                if (b->d_stream_owned) GSH_HIP(hipFree(b->d_stream_owned));
-                b->d_stream_owned = nullptr;
-                b->stream_owned_cap = 0;
-                GSH_HIP(hipMalloc(&b->d_stream_owned, sizeof(float2) * need));
-                b->stream_owned_cap = need;
-            }
-        GSH_HIP(hipMemcpy(b->d_stream_owned, iq, sizeof(float2) * n_samples, hipMemcpyHostToDevice));
-        GSH_HIP(hipMemset(b->d_stream_owned + n_samples, 0, sizeof(float2) * 2));
-        b->d_stream = b->d_stream_owned;
+        GSH_TRY(b->stream_owned.grow(static_cast<size_t>(n_samples) + 2));  // one spare pair: 16-byte loads may touch sample n
+        GSH_HIP(hipMemcpy(b->stream_owned.p, iq, sizeof(float2) * n_samples, hipMemcpyHostToDevice));
+        GSH_HIP(hipMemset(b->stream_owned.p + n_samples, 0, sizeof(float2) * 2));
+        b->d_stream = b->stream_owned.p;
         b->stream_len = n_samples;
         b->ring = nullptr;
         return GSH_OK;
@@ -640,7 +630,7 @@ extern "C"
     {
         GSH_REQUIRE(b != nullptr, "null bank");
         b->fusion_user = enable ? 1 : 0;
-        b->n_jobs = 0;  // the staged batch was analysed under the previous setting
+        b->batch.invalidate();  // the staged batch was analysed under the previous setting
         return GSH_OK;
     }
 
@@ -649,14 +639,9 @@ extern "C"
         GSH_REQUIRE(b != nullptr, "null bank");
         GSH_REQUIRE(n_jobs >= 0, "n_jobs %d", n_jobs);
         GSH_REQUIRE(n_jobs == 0 || jobs != nullptr, "null jobs");
-        b->n_jobs = 0;
+        b->batch.invalidate();
         if (n_jobs == 0) return GSH_OK;
-        int rc = bank_stage_jobs(b, jobs, n_jobs);
-        if (rc != GSH_OK)
-            {
-                b->n_jobs = 0;
-                return rc;
-            }
+        GSH_TRY(bank_stage_jobs(b, jobs, n_jobs));
         GSH_HIP(hipStreamSynchronize(b->stream));
         return GSH_OK;
     }
@@ -666,96 +651,36 @@ extern "C"
         GSH_REQUIRE(b != nullptr, "null bank");
         GSH_REQUIRE(s == nullptr || s->device == b->device, "the ring lives on device %d, the bank on device %d", s ? s->device : -1, b->device);
         b->ring = s;
-        b->n_jobs = 0;  // an uploaded job table was translated against the previous attachment
-        if (s != nullptr)
-            {
-                b->d_stream = s->d_ring;
-                b->stream_len = s->capacity + s->max_window;
-            }
-        else
-            {
-                b->d_stream = nullptr;
-                b->stream_len = 0;
-            }
+        b->batch.invalidate();  // an uploaded job table was translated against the previous attachment
+        b->d_stream = s != nullptr ? s->d_ring : nullptr;
+        b->stream_len = s != nullptr ? s->capacity + s->max_window : 0;
         return GSH_OK;
     }
 
+    // check, reserve the partials, fill the arguments, wait for the push, regroup if the fusion verdict changed, launch, mark the ring read
     int gsh_bank_launch(gsh_bank_t* b, void* hip_stream)
     {
         GSH_REQUIRE(b != nullptr, "null bank");
-        if (b->n_jobs == 0) return GSH_OK;
-        if (b->d_stream == nullptr) return set_error(GSH_ERR_STATE, "no sample stream attached (gsh_bank_set_stream_*)");
-        if (b->ring == nullptr)
-            {
-                if (b->max_end + b->sample_base > b->stream_len)  // sample_base shifts every window (gsh_bank_set_sample_base)
-                    return set_error(GSH_ERR_INVALID, "a job window ends at sample %llu (sample_base %llu), past the %llu-sample stream", b->max_end + b->sample_base,
-                        b->sample_base, b->stream_len);
-            }
-        else if (b->ring_max_end != 0)
-            {
-                // the shifted windows must be resident and pushed: a base that points at samples the ring no longer (or not yet) holds would make
-                // the kernel read whatever lives at those ring positions now
-                const unsigned long long lo = b->ring_min_start + b->sample_base, hi = b->ring_max_end + b->sample_base;
-                if (lo < gsh::stream_oldest(b->ring) || hi > b->ring->next)
-                    return set_error(GSH_ERR_INVALID, "windows [%llu, %llu) (sample_base %llu) are not resident (ring holds [%llu, %llu))", lo, hi, b->sample_base,
-                        gsh::stream_oldest(b->ring), static_cast<unsigned long long>(b->ring->next));
-            }
+        StagedBatch& batch = b->batch;
+        if (batch.n_jobs == 0) return GSH_OK;
+        GSH_TRY(bank_may_launch(b));
         GSH_HIP(hipSetDevice(b->device));
         const int splits = bank_splits(b);
-        if (splits > 1)
-            {
-                const size_t need = static_cast<size_t>(b->n_jobs) * splits * GSH_MAX_TAPS;
-                if (need > b->partials_cap)
-                    {
-                        if (b->d_partials) GSH_HIP(hipFree(b->d_partials));
-                        b->d_partials = nullptr;
-                        b->partials_cap = 0;
-                        GSH_HIP(hipMalloc(&b->d_partials, sizeof(float2) * need));
-                        b->partials_cap = need;
-                    }
-            }
-        gsh::McorrArgs a;
-        a.stream = b->d_stream;
-        a.stream_len = b->stream_len;
-        a.jobs = b->d_jobs;
-        a.codes = b->d_codes;
-        a.code_lens = b->d_code_lens;
-        a.code_stride = b->max_code_len;
-        a.code_images = b->d_code_images;
-        a.out = b->d_out;
-        a.partials = b->d_partials;
-        a.n_jobs = b->n_jobs;
-        a.splits = splits;
-        a.window_floats = bank_window_floats(b, splits);
-        a.packed = gsh::mcorr_packed_default();
-        a.fac = gsh::mcorr_fac_default();
-        a.pair = b->pair ? 1 : 0;
-        a.half = b->half ? 1 : 0;
-        a.sample_base = b->sample_base;
-        a.ring_capacity = b->ring != nullptr ? b->ring->capacity : 0ull;
-        // the second code table must not cost the occupancy the fusion is meant to win: only with windowed tables or short codes
-        const bool fuse = b->n_fused > 0 && (a.window_floats > 0 || static_cast<size_t>(b->max_code_len) * sizeof(float) <= 10 * 1024);
-        a.aux = fuse ? b->d_aux : nullptr;
+        if (splits > 1) GSH_TRY(b->partials.grow(static_cast<size_t>(batch.n_jobs) * splits * GSH_MAX_TAPS));
+        const gsh::McorrArgs a = bank_launch_args(b, splits);
+        const bool fuse = a.aux != nullptr;
         hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : b->stream;
-        if (b->ring != nullptr)
+        // wait for the push that completed this batch's newest window -- not for a later block that may already be on its way
+        if (b->ring != nullptr) GSH_TRY(gsh::stream_wait_pushed(b->ring, batch.ring_max_end ? batch.ring_max_end + b->sample_base : ~0ull, s));
+        if (batch.lists_fused != fuse)
             {
-                // wait for the push that completed this batch's newest window -- not for a later block that may already be on its way
-                int rcw = gsh::stream_wait_pushed(b->ring, b->ring_max_end ? b->ring_max_end + b->sample_base : ~0ull, s);
-                if (rcw != GSH_OK) return rcw;
-            }
-        a.job_list = nullptr;
-        a.n_launch = b->n_jobs;
-        if (b->lists_fused != fuse)
-            {
-                // the LDS rule above changed its verdict since the batch was staged (set_splits in between): regroup
-                int rc2 = bank_build_lists(b, fuse);
-                if (rc2 != GSH_OK) return rc2;
+                // the LDS rule of bank_launch_args changed its verdict since the batch was staged (set_splits in between): regroup
+                GSH_TRY(bank_build_lists(b, batch, fuse));
                 GSH_HIP(hipStreamSynchronize(b->stream));  // the list upload was queued on the bank's stream
             }
-        const int rc_launch = b->use_classes ? gsh::mcorr_launch_classes(a, b->class_plan, b->mode, b->max_code_len, s)
-                                             : gsh::mcorr_launch(a, b->max_taps, b->mode, b->max_code_len, s);
-        if (rc_launch != GSH_OK) return rc_launch;
-        if (b->ring != nullptr) return gsh::stream_mark_read(b->ring, b->ring_min_start + b->sample_base, s);  // pushes that would overwrite these windows wait
+        GSH_TRY(batch.use_classes ? gsh::mcorr_launch_classes(a, batch.class_plan, batch.mode, b->max_code_len, s)
+                                  : gsh::mcorr_launch(a, batch.max_taps, batch.mode, b->max_code_len, s));
+        if (b->ring != nullptr) return gsh::stream_mark_read(b->ring, batch.ring_min_start + b->sample_base, s);  // pushes that would overwrite these windows wait
         return GSH_OK;
     }
 
@@ -770,10 +695,10 @@ extern "C"
     int gsh_bank_read_outputs(gsh_bank_t* b, float* out_iq, int n_jobs)
     {
         GSH_REQUIRE(b && out_iq, "null argument");
-        GSH_REQUIRE(n_jobs >= 0 && n_jobs <= b->n_jobs, "n_jobs %d outside 0..%d", n_jobs, b->n_jobs);
+        GSH_REQUIRE(n_jobs >= 0 && n_jobs <= b->batch.n_jobs, "n_jobs %d outside 0..%d", n_jobs, b->batch.n_jobs);
         if (n_jobs == 0) return GSH_OK;
         GSH_HIP(hipSetDevice(b->device));
-        GSH_HIP(hipMemcpyAsync(out_iq, b->d_out, sizeof(float2) * GSH_MAX_TAPS * static_cast<size_t>(n_jobs), hipMemcpyDeviceToHost, b->stream));
+        GSH_HIP(hipMemcpyAsync(out_iq, b->out.p, sizeof(float2) * GSH_MAX_TAPS * static_cast<size_t>(n_jobs), hipMemcpyDeviceToHost, b->stream));
         GSH_HIP(hipStreamSynchronize(b->stream));
         return GSH_OK;
     }
@@ -784,21 +709,11 @@ extern "C"
         GSH_REQUIRE(b != nullptr, "null bank");
         GSH_REQUIRE(n_jobs >= 0, "n_jobs %d", n_jobs);
         GSH_REQUIRE(n_jobs == 0 || (jobs != nullptr && out_iq != nullptr), "null argument");
-        b->n_jobs = 0;
+        b->batch.invalidate();
         if (n_jobs == 0) return GSH_OK;
-        int rc = bank_stage_jobs(b, jobs, n_jobs);
-        if (rc == GSH_OK) rc = gsh_bank_launch(b, nullptr);
-        if (rc != GSH_OK)
-            {
-                (void)hipStreamSynchronize(b->stream);
-                b->n_jobs = 0;
-                return rc;
-            }
+        const int rc = bank_run(b, jobs, n_jobs);
         const size_t bytes = sizeof(float2) * GSH_MAX_TAPS * static_cast<size_t>(n_jobs);
-        GSH_HIP(hipMemcpyAsync(b->h_out, b->d_out, bytes, hipMemcpyDeviceToHost, b->stream));
-        GSH_HIP(hipStreamSynchronize(b->stream));
-        std::memcpy(out_iq, b->h_out, bytes);
-        return GSH_OK;
+        return bank_fetch(b, rc, true, b->out.p, b->h_out.p, bytes, out_iq, bytes);
     }
 
     int gsh_bank_time_launches(gsh_bank_t* b, int reps, float* avg_ms)
@@ -806,20 +721,8 @@ extern "C"
         GSH_REQUIRE(b && avg_ms, "null argument");
         GSH_REQUIRE(reps >= 1, "reps %d", reps);
         GSH_HIP(hipSetDevice(b->device));
-        int rc = gsh_bank_launch(b, nullptr);  // warm-up, also validates state
-        if (rc != GSH_OK) return rc;
-        GSH_HIP(hipEventRecord(b->ev0, b->stream));
-        for (int i = 0; i < reps; i++)
-            {
-                rc = gsh_bank_launch(b, nullptr);
-                if (rc != GSH_OK) return rc;
-            }
-        GSH_HIP(hipEventRecord(b->ev1, b->stream));
-        GSH_HIP(hipEventSynchronize(b->ev1));
-        float ms = 0.0f;
-        GSH_HIP(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-        *avg_ms = ms / static_cast<float>(reps);
-        return GSH_OK;
+        GSH_TRY(gsh_bank_launch(b, nullptr));  // warm-up, also validates state
+        return gsh::time_launches(b->ev0, b->ev1, b->stream, reps, avg_ms, [b] { return gsh_bank_launch(b, nullptr); });
     }
 
     int gsh_bank_correlate_wide(gsh_bank_t* b, const gsh_corr_job_wide* jobs, int n_jobs, float* out_iq)
@@ -830,18 +733,9 @@ extern "C"
         GSH_REQUIRE(n_jobs == 0 || (jobs != nullptr && out_iq != nullptr), "null argument");
         if (n_jobs == 0) return GSH_OK;
         WidePlan plan;
-        int rc = bank_stage_wide(b, jobs, n_jobs, &plan);
-        if (rc == GSH_OK) rc = bank_launch_wide(b, n_jobs, plan);
-        if (rc != GSH_OK)
-            {
-                (void)hipStreamSynchronize(b->stream);
-                return rc;
-            }
+        const int rc = bank_run_wide(b, jobs, n_jobs, &plan);
         const size_t bytes = sizeof(float2) * GSH_MAX_WIDE_TAPS * static_cast<size_t>(n_jobs);
-        GSH_HIP(hipMemcpyAsync(b->h_wout, b->d_wout, bytes, hipMemcpyDeviceToHost, b->stream));
-        GSH_HIP(hipStreamSynchronize(b->stream));
-        std::memcpy(out_iq, b->h_wout, bytes);
-        return GSH_OK;
+        return bank_fetch(b, rc, false, b->wout.p, b->h_wout.p, bytes, out_iq, bytes);
     }
 
     int gsh_bank_time_launches_wide(gsh_bank_t* b, const gsh_corr_job_wide* jobs, int n_jobs, int reps, float* avg_ms)
@@ -850,24 +744,10 @@ extern "C"
         GSH_REQUIRE(n_jobs >= 1 && jobs != nullptr, "no jobs");
         GSH_REQUIRE(reps >= 1, "reps %d", reps);
         WidePlan plan;
-        int rc = bank_stage_wide(b, jobs, n_jobs, &plan);
-        if (rc == GSH_OK) rc = bank_launch_wide(b, n_jobs, plan);  // warm-up
-        if (rc == GSH_OK)
-            {
-                GSH_HIP(hipEventRecord(b->ev0, b->stream));
-                for (int i = 0; i < reps && rc == GSH_OK; i++) rc = bank_launch_wide(b, n_jobs, plan);
-            }
-        if (rc != GSH_OK)
-            {
-                (void)hipStreamSynchronize(b->stream);
-                return rc;
-            }
-        GSH_HIP(hipEventRecord(b->ev1, b->stream));
-        GSH_HIP(hipEventSynchronize(b->ev1));
-        float ms = 0.0f;
-        GSH_HIP(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-        *avg_ms = ms / static_cast<float>(reps);
-        return GSH_OK;
+        int rc = bank_run_wide(b, jobs, n_jobs, &plan);  // its launch is the warm-up
+        if (rc == GSH_OK) rc = gsh::time_launches(b->ev0, b->ev1, b->stream, reps, avg_ms, [&] { return bank_launch_wide(b, n_jobs, plan); });
+        if (rc != GSH_OK) (void)hipStreamSynchronize(b->stream);
+        return rc;
     }
 }
 
@@ -892,47 +772,51 @@ struct gsh_mcorr
 
 namespace
 {
-// more than GSH_MAX_TAPS correlators: one job of the wide bank (standard resampler and rotator only)
-int mcorr_run_wide(gsh_mcorr* h, int mode, float rem_carr, float phase_step, float rem_code, float code_step, int n)
+// the one job of a call, as far as both job records go: the whole epoch, slot 0, the taps as the caller's array holds them now
+template <typename Job>
+Job mcorr_job(const gsh_mcorr* h, float rem_carr, float phase_step, float rem_code, float code_step, int n)
 {
-    gsh_bank* b = h->bank;
-    if (mode != 0)
-        {
-            // the reference leaves valid results behind every call; a caller that does not look at the status must not see the previous epoch's
-            std::memset(h->corr_out, 0, sizeof(float2) * static_cast<size_t>(h->n_correlators));
-            return set_error(GSH_ERR_UNSUPPORTED,
-                "%d correlators: more than %d run the wide bank, which has the standard resampler only -- call set_high_dynamics_resampler(false)", h->n_correlators,
-                GSH_MAX_TAPS);
-        }
-    gsh_corr_job_wide j;
+    Job j;
     std::memset(&j, 0, sizeof(j));
-    j.sample_offset = 0;
     j.n_samples = n;
-    j.code_slot = 0;
     j.rem_carr_phase_rad = rem_carr;
     j.phase_step_rad = phase_step;
     j.rem_code_phase_chips = rem_code;
     j.code_phase_step_chips = code_step;
     j.n_taps = h->n_correlators;
     for (int t = 0; t < h->n_correlators; t++) j.shifts_chips[t] = h->shifts[t];
+    return j;
+}
 
+// the epoch through pinned staging onto the device, queued on the bank's stream, and attached as the bank's stream
+int mcorr_attach_epoch(gsh_mcorr* h, int n)
+{
     std::memcpy(h->h_pinned_in, h->sig_in, sizeof(float2) * static_cast<size_t>(n));
-    GSH_HIP(hipMemcpyAsync(h->d_in, h->h_pinned_in, sizeof(float2) * static_cast<size_t>(n), hipMemcpyHostToDevice, b->stream));
-    b->d_stream = h->d_in;
-    b->stream_len = static_cast<unsigned long long>(n);
-    WidePlan plan;
-    int rc = bank_stage_wide(b, &j, 1, &plan);
-    if (rc == GSH_OK) rc = bank_launch_wide(b, 1, plan);
-    if (rc != GSH_OK)
-        {
-            (void)hipStreamSynchronize(b->stream);
-            std::memset(h->corr_out, 0, sizeof(float2) * static_cast<size_t>(h->n_correlators));
-            return rc;
-        }
-    GSH_HIP(hipMemcpyAsync(h->h_pinned_out, b->d_wout, sizeof(float2) * GSH_MAX_WIDE_TAPS, hipMemcpyDeviceToHost, b->stream));
-    GSH_HIP(hipStreamSynchronize(b->stream));
-    std::memcpy(h->corr_out, h->h_pinned_out, sizeof(float2) * static_cast<size_t>(h->n_correlators));
+    GSH_HIP(hipMemcpyAsync(h->d_in, h->h_pinned_in, sizeof(float2) * static_cast<size_t>(n), hipMemcpyHostToDevice, h->bank->stream));
+    h->bank->d_stream = h->d_in;
+    h->bank->stream_len = static_cast<unsigned long long>(n);
     return GSH_OK;
+}
+
+// more than GSH_MAX_TAPS correlators: one job of the wide bank (standard resampler and rotator only)
+int mcorr_run_wide(gsh_mcorr* h, int mode, float rem_carr, float phase_step, float rem_code, float code_step, int n)
+{
+    gsh_bank* b = h->bank;
+    int rc = mode == 0 ? GSH_OK
+                       : set_error(GSH_ERR_UNSUPPORTED,
+                             "%d correlators: more than %d run the wide bank, which has the standard resampler only -- call set_high_dynamics_resampler(false)",
+                             h->n_correlators, GSH_MAX_TAPS);
+    if (rc == GSH_OK) rc = mcorr_attach_epoch(h, n);
+    if (rc == GSH_OK)
+        {
+            const gsh_corr_job_wide j = mcorr_job<gsh_corr_job_wide>(h, rem_carr, phase_step, rem_code, code_step, n);
+            WidePlan plan;
+            rc = bank_run_wide(b, &j, 1, &plan);
+            rc = bank_fetch(b, rc, false, b->wout.p, h->h_pinned_out, sizeof(float2) * GSH_MAX_WIDE_TAPS, h->corr_out, sizeof(float2) * static_cast<size_t>(h->n_correlators));
+        }
+    // the reference leaves valid results behind every call; a caller that does not look at the status must not see the previous epoch's
+    if (rc != GSH_OK) std::memset(h->corr_out, 0, sizeof(float2) * static_cast<size_t>(h->n_correlators));
+    return rc;
 }
 
 int mcorr_run(gsh_mcorr* h, int mode, float rem_carr, float phase_step, float phase_rate, float rem_code, float code_step, float code_rate, int n)
@@ -946,39 +830,14 @@ int mcorr_run(gsh_mcorr* h, int mode, float rem_carr, float phase_step, float ph
     GSH_HIP(hipSetDevice(h->device));
     if (h->n_correlators > GSH_MAX_TAPS) return mcorr_run_wide(h, mode, rem_carr, phase_step, rem_code, code_step, n);
 
-    gsh_corr_job j;
-    std::memset(&j, 0, sizeof(j));
-    j.sample_offset = 0;
-    j.n_samples = n;
-    j.code_slot = 0;
-    j.rem_carr_phase_rad = rem_carr;
-    j.phase_step_rad = phase_step;
+    gsh_corr_job j = mcorr_job<gsh_corr_job>(h, rem_carr, phase_step, rem_code, code_step, n);
     j.phase_rate_step_rad = phase_rate;
-    j.rem_code_phase_chips = rem_code;
-    j.code_phase_step_chips = code_step;
     j.code_phase_rate_step_chips = code_rate;
-    j.n_taps = h->n_correlators;
     j.high_dyn = mode;
-    for (int t = 0; t < h->n_correlators; t++) j.shifts_chips[t] = h->shifts[t];
-
-    // H2D of the epoch through pinned staging, one launch, D2H of T complex values
-    std::memcpy(h->h_pinned_in, h->sig_in, sizeof(float2) * static_cast<size_t>(n));
-    GSH_HIP(hipMemcpyAsync(h->d_in, h->h_pinned_in, sizeof(float2) * static_cast<size_t>(n), hipMemcpyHostToDevice, b->stream));
-    b->d_stream = h->d_in;
-    b->stream_len = static_cast<unsigned long long>(n);
-    // one synchronisation per call: pinned job record -> H2D, kernel and D2H are all queued on the bank's stream
-    int rc = bank_stage_jobs(b, &j, 1);
-    if (rc == GSH_OK) rc = gsh_bank_launch(b, nullptr);
-    if (rc != GSH_OK)
-        {
-            (void)hipStreamSynchronize(b->stream);
-            b->n_jobs = 0;
-            return rc;
-        }
-    GSH_HIP(hipMemcpyAsync(h->h_pinned_out, b->d_out, sizeof(float2) * GSH_MAX_TAPS, hipMemcpyDeviceToHost, b->stream));
-    GSH_HIP(hipStreamSynchronize(b->stream));
-    std::memcpy(h->corr_out, h->h_pinned_out, sizeof(float2) * static_cast<size_t>(h->n_correlators));
-    return GSH_OK;
+    // one synchronisation per call: the epoch and the job record H2D, the kernel and D2H of T complex values are all queued on the bank's stream
+    GSH_TRY(mcorr_attach_epoch(h, n));
+    const int rc = bank_run(b, &j, 1);
+    return bank_fetch(b, rc, true, b->out.p, h->h_pinned_out, sizeof(float2) * GSH_MAX_TAPS, h->corr_out, sizeof(float2) * static_cast<size_t>(h->n_correlators));
 }
 }  // namespace
 
