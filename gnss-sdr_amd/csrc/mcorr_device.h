@@ -77,6 +77,12 @@ constexpr int MC_HALF_WORDS = 2 * (MC_HALF_MAX_CODE_LEN + 2 * MC_MARGIN);  // 2 
 #define GSH_MC_PAIR_BARRIER 1  // the scheduling barrier between the two trips of a pair with two trips of loads in flight; 0: the second trip's chains may start under the first
                                // one's accumulates (measured, round 10, profiles/r10_summary.txt: the same 90 VGPRs, 0.1 % slower in each of seven alternating pairs)
 #endif
+#ifndef GSH_MC_ANCHOR_FMA
+#define GSH_MC_ANCHOR_FMA 1  // half-chip trips (run_segment_packed, round 13): the sample numbers a trip's chains start from are ONE running float per lane, chunk A's of a
+                             // single trip or of the first trip of a pair; chunk B's and the second trip's products come from it by v_pk_fma_f32 with a wave-uniform
+                             // constant step' K (K a power of two: exact, so the FMA rounds step' (n + K) once, as the multiply did).  0: one float per chunk, each
+                             // stepped every trip, as in rounds 7 - 12
+#endif
 #ifndef GSH_MC_DER_MIXED
 #define GSH_MC_DER_MIXED 0  // 1: in a trip with one unsafe chunk the other chunk still pairs its taps (two more loop bodies: measured, the register
                             // allocator then spills and the launch is 45 % slower -- profiles/r02/paired_taps.txt)
@@ -535,6 +541,26 @@ __device__ __forceinline__ v2f pk_add_shi(v2f v, v2f k)
     return r;
 }
 
+// v * k.lo + c.lo / + c.hi / - c.lo per component: k in VGPRs, c wave-uniform (the one SGPR pair a VOP3P instruction of gfx9 may read)
+__device__ __forceinline__ v2f pk_fma_vlo_slo(v2f v, v2f k, v2f c)
+{
+    v2f r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(v), "v"(k), "s"(c));
+    return r;
+}
+__device__ __forceinline__ v2f pk_fma_vlo_shi(v2f v, v2f k, v2f c)
+{
+    v2f r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(v), "v"(k), "s"(c));
+    return r;
+}
+__device__ __forceinline__ v2f pk_fma_vlo_nslo(v2f v, v2f k, v2f c)
+{
+    v2f r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(k), "s"(c));
+    return r;
+}
+
 // One trip of the packed path: NCH chunks of MC_PAIRS_PER_CHUNK pairs; lane `tid` owns the pair tid of each chunk.  The caller hands over
 // the four samples (already zero where they lie outside the segment) and the sample indices the chip look-ups use (nfA / nfB: (float)n of
 // the pair; for a sample outside the segment the caller passes the nearest index INSIDE it, so that its look-up stays within what is
@@ -555,12 +581,14 @@ __device__ __forceinline__ v2f pk_add_shi(v2f v, v2f k)
 //     the per-tap chains for that trip as before.
 // The products and their order of summation are the same either way: the outputs are bit-identical with the switch off
 // (tests/test_tracking_gpu.py::test_paired_taps_are_bit_identical).
-template <int NT, bool ZP, bool AUX, int NCH, bool PA = false, bool PB = false, bool KC = false, bool HALF = false>
+// (PROD, half-chip trips only: nfA / nfB are already the scaled products step' n of the two chunks -- the caller forms them from one anchor, GSH_MC_ANCHOR_FMA)
+template <int NT, bool ZP, bool AUX, int NCH, bool PA = false, bool PB = false, bool KC = false, bool HALF = false, bool PROD = false>
 __device__ __forceinline__ void packed_trip(const JobCtx& c, const float* __restrict__ tab, const v2f (&shp)[NT],
     v2f k_step_nrem, v2f aux_shp, bool aux_on, v2f nfA, v2f nfB, v2f yA0, v2f yA1, v2f yB0, v2f yB1, v2f (&A0)[NT], v2f (&A1)[NT], v2f (&B0)[NT],
     v2f (&B1)[NT], v2f& XA0, v2f& XA1, v2f& XB0, v2f& XB1, v2f scaled_step_nrem = (v2f){0.0f, 0.0f}, v2f scaled_shP_shL = (v2f){0.0f, 0.0f})
 {
     static_assert(!(PA || PB) || NT == 3, "paired taps: early / prompt / late");
+    static_assert(!PROD || (HALF && PA && PB), "scaled products: the half-chip trip");
     static_assert(!HALF || (GSH_MC_PKRTZ && KC && ZP && !AUX && NCH == 2 && NT == 3), "half-chip taps: E/P/L, zero-shift prompt, whole-code table, two chunks per trip");
     constexpr int TB = HALF ? MC_HALF_WORDS : 0;  // word offset of the plain table (KC: a constant; the doubled table of the half-chip flavour lies in front of it)
     const v2f zero = {0.0f, 0.0f};
@@ -674,8 +702,17 @@ __device__ __forceinline__ void packed_trip(const JobCtx& c, const float* __rest
                     // and in the doubled table D[h] = code[h >> 1] the three code values are the consecutive words D[h - 1], D[h], D[h + 1].  The chain runs on constants
                     // scaled by 2^-23 (the caller's), so the half-precision pattern of v_cvt_pkrtz_f16_f32 IS floor(2 w) for 2 w < 2048: per chunk one multiply, one add,
                     // one conversion and two address shifts instead of two chains.  Same products into the same accumulators as the forms below.
-                    const v2f uA = pk_add_shi(pk_mul_slo(nfA, scaled_step_nrem), scaled_step_nrem);
-                    const v2f uB = pk_add_shi(pk_mul_slo(nfB, scaled_step_nrem), scaled_step_nrem);
+                    v2f uA, uB;
+                    if constexpr (PROD)
+                        {
+                            uA = pk_add_shi(nfA, scaled_step_nrem);
+                            uB = pk_add_shi(nfB, scaled_step_nrem);
+                        }
+                    else
+                        {
+                            uA = pk_add_shi(pk_mul_slo(nfA, scaled_step_nrem), scaled_step_nrem);
+                            uB = pk_add_shi(pk_mul_slo(nfB, scaled_step_nrem), scaled_step_nrem);
+                        }
                     auto two_halves = [](v2f u, unsigned& byte0, unsigned& byte1) {
                         unsigned pk;
                         asm("v_cvt_pkrtz_f16_f32 %0, %1, %2" : "=v"(pk) : "v"(u.x), "v"(u.y));
@@ -1097,15 +1134,33 @@ __device__ __forceinline__ void run_segment_packed(const Ctx& c, const float2* _
     auto uniform = [](float x) -> float { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); };  // (a product is a VGPR value)
     const v2f scaled_step_nrem = {uniform(c.code_step * PK_SCALE), uniform(-c.rem_code * PK_SCALE)};
     const v2f scaled_shP_shL = {uniform(sh[NT / 2] * PK_SCALE), uniform(sh[NT - 1] * PK_SCALE)};
-    const bool scaled_ok = scales_exactly(c.code_step) && scales_exactly(c.rem_code) && scales_exactly(sh[NT / 2]) && scales_exactly(sh[NT - 1]);  // uniform
+    const bool scales_ok = scales_exactly(c.code_step) && scales_exactly(c.rem_code) && scales_exactly(sh[NT / 2]) && scales_exactly(sh[NT - 1]);  // uniform
+    // ONE ANCHOR PER LANE (round 13, half-chip trips).  A trip's two chunks, and the two trips of a pair, look at samples n, n + 2 PPC, n + TRIP and n + TRIP + 2 PPC:
+    // one number plus constants.  For K a power of two step' K is exact, so v_pk_fma_f32 gives fl(step' n + step' K) = fl(step' (n + K)): the real number the
+    // multiply of (float)(n + K) rounds, rounded once -- the same bits -- and the float of chunk B with its step per trip is not kept.  3 * 2 PPC is no power of
+    // two (step' K would be rounded when formed): the second trip's chunk B is reached from the anchor stepped by 2 TRIP, minus 2 PPC.
+    constexpr bool ANCHOR = GSH_MC_ANCHOR_FMA && HALF && NCH == 2;
+    v2f anchor_chunk_trip = {0.0f, 0.0f};  // step' 2 PPC, step' TRIP: wave-uniform
+    bool anchor_ok = true;                 // both, and the anchor's step per pass times step', normal and finite: otherwise the per-tap chains, as for a denormal constant
+    if constexpr (ANCHOR)
+        {
+            const float c_chunk = c.code_step * (PK_SCALE * static_cast<float>(2 * PPC)), c_trip = c.code_step * (PK_SCALE * static_cast<float>(TRIP));
+            anchor_chunk_trip = (v2f){uniform(c_chunk), uniform(c_trip)};
+            auto normal_finite = [](float x) -> bool { return fabsf(x) >= 0x1p-126f && fabsf(x) < __builtin_inff(); };
+            anchor_ok = normal_finite(c_chunk) && normal_finite(c_trip) && normal_finite(c.code_step * (PK_SCALE * static_cast<float>(2 * TRIP)));
+        }
+    const bool scaled_ok = scales_ok && anchor_ok;  // uniform
 #else
     const v2f scaled_step_nrem = {0.0f, 0.0f}, scaled_shP_shL = {0.0f, 0.0f};
+    constexpr bool ANCHOR = false;
+    const v2f anchor_chunk_trip = {0.0f, 0.0f};
 #endif
     v2f shp[NT];
 #pragma unroll
     for (int t = 0; t < NT; t++) shp[t] = (v2f){sh[t], sh[t]};
     const v2f aux_shp = {c.aux_shift, c.aux_shift};
     const v2f stride = {static_cast<float>(2 * NCH * PPC), static_cast<float>(2 * NCH * PPC)};
+    const v2f stride2 = {static_cast<float>(4 * NCH * PPC), static_cast<float>(4 * NCH * PPC)};  // (ANCHOR: a pair of trips)
     const bool aux_on = AUX && c.aux_on;
     const double sd = static_cast<double>(c.phase_step);
 
@@ -1278,13 +1333,15 @@ __device__ __forceinline__ void run_segment_packed(const Ctx& c, const float2* _
                 else
                     pa = pk_cmul(table(4 + r_idx - tbl0), L);
                 nfA = (v2f){static_cast<float>(n0), static_cast<float>(n0 + 1)};
-                nfB = (v2f){static_cast<float>(n0 + 2 * PPC), static_cast<float>(n0 + 2 * PPC + 1)};
+                if constexpr (!ANCHOR) nfB = (v2f){static_cast<float>(n0 + 2 * PPC), static_cast<float>(n0 + 2 * PPC + 1)};
                 until_reseed = RESEED;
                 r_idx++;
             }
         until_reseed--;
         const bool plain = KP || ((i >= first_plain) && (i < last_plain));  // uniform
         v2f ia = nfA, ib = nfB;
+        // (ANCHOR: chunk B's number is not kept; the trips that are not half-chip trips form it here, in their cold blocks)
+        if constexpr (ANCHOR && !(FA && FB)) ib = nfA + (v2f){static_cast<float>(2 * PPC), static_cast<float>(2 * PPC)};
         if (!(FA || FB) && !plain)  // (derived trips are plain ones)
             {
                 // edge trip: a sample outside the segment (already zero) is looked up at the nearest sample inside it, so that its
@@ -1358,12 +1415,35 @@ __device__ __forceinline__ void run_segment_packed(const Ctx& c, const float2* _
             }
         else if constexpr (MRG)  // (one set: the four references name the same registers, the accumulates follow one another)
             packed_trip<NT, ZP, AUX, NCH, FA, FB, KC>(c, tab, shp, k_step_nrem, aux_shp, aux_on, ia, ib, yA0, yA1, yB0, yB1, A0, A0, A0, A0, XA0, XA0, XA0, XA0);
+        else if constexpr (ANCHOR && FA && FB)
+            {
+                // a half-chip trip: the scaled products step' n of its two chunks from the anchor -- a single trip's or a pair's first trip's own chunk A (one multiply,
+                // one FMA); a pair's second trip from the first trip's anchor, which is stepped ONCE per pass behind this trip's chunk-A product, chunk B taken back
+                // from the stepped one (two FMAs, one add).  Every constant times step' is exact (scaled_ok), so each product is the multiply's, bit for bit.
+                v2f prodA, prodB;
+                if constexpr (PM < 2)
+                    {
+                        prodA = pk_mul_slo(nfA, scaled_step_nrem);
+                        prodB = pk_fma_vlo_slo(nfA, scaled_step_nrem, anchor_chunk_trip);
+                    }
+                else
+                    {
+                        prodA = pk_fma_vlo_shi(nfA, scaled_step_nrem, anchor_chunk_trip);
+                        asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfA) : "s"(stride2));
+                        prodB = pk_fma_vlo_nslo(nfA, scaled_step_nrem, anchor_chunk_trip);
+                    }
+                packed_trip<NT, ZP, AUX, NCH, FA, FB, KC, HALF, true>(c, tab, shp, k_step_nrem, aux_shp, aux_on, prodA, prodB, yA0, yA1, yB0, yB1, A0, A1, B0, B1, XA0,
+                    XA1, XB0, XB1, scaled_step_nrem, scaled_shP_shL);
+            }
         else
             packed_trip<NT, ZP, AUX, NCH, FA, FB, KC, HALF>(c, tab, shp, k_step_nrem, aux_shp, aux_on, ia, ib, yA0, yA1, yB0, yB1, A0, A1, B0, B1, XA0, XA1, XB0, XB1,
                 scaled_step_nrem, scaled_shP_shL);
         pa = pk_cmul_s(pa, w2);  // (w2 and the stride are wave-uniform: straight from SGPRs, not copied into VGPRs every trip)
-        asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfA) : "s"(stride));
-        if (NCH == 2) asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfB) : "s"(stride));
+        if constexpr (ANCHOR && PM != 0)
+            ;  // (a pair steps its anchor once, inside its second trip)
+        else
+            asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfA) : "s"(stride));
+        if (NCH == 2 && !ANCHOR) asm("v_pk_add_f32 %0, %0, %1" : "+v"(nfB) : "s"(stride));
     };
     using no = integral_constant<bool, false>;
     using yes = integral_constant<bool, true>;
