@@ -17,6 +17,8 @@ GSH_OK = 0
 GSH_ITEM_GR_COMPLEX, GSH_ITEM_SHORT, GSH_ITEM_BYTE = 0, 1, 2
 GSH_ARRAY_MAX_ANTENNAS, GSH_ARRAY_MAX_BEAMS = 8, 8
 GSH_ARRAY_PLANAR, GSH_ARRAY_INTERLEAVED = 0, 1
+GSH_TLM_METRIC_FULL, GSH_TLM_METRIC_REFERENCE = 0, 1
+GSH_TLM_JOB_INVERT, GSH_TLM_JOB_CRC_CONTINUE, GSH_TLM_JOB_INAV_AUTO = 1, 2, 4
 ERR_NAMES = {1: "GSH_ERR_INVALID", 2: "GSH_ERR_NO_DEVICE", 3: "GSH_ERR_HIP", 4: "GSH_ERR_STATE", 5: "GSH_ERR_UNSUPPORTED"}
 
 
@@ -284,6 +286,28 @@ class CondNotchState(C.Structure):
     ]
 
 
+class TlmPageJob(C.Structure):
+    """gsh_tlm_page_job (32 bytes)."""
+    _fields_ = [
+        ("channel", C.c_int32),
+        ("frame_type", C.c_int32),
+        ("symbol_offset", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("crc_bits", C.c_int32),
+        ("crc_check", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class TlmPageResult(C.Structure):
+    """gsh_tlm_page_result (72 bytes)."""
+    _fields_ = [
+        ("bits", C.c_uint32 * 16),
+        ("crc_register", C.c_uint32),
+        ("crc_ok", C.c_int32),
+    ]
+
+
 class AcqResult(C.Structure):
     """gsh_acq_result."""
     _fields_ = [
@@ -515,6 +539,14 @@ SYMBOLS = {
     "gsh_acq_time_dwells": (C.c_int, [_P, C.c_uint32, C.c_int, _F]),
     "gsh_acq_time_dwells_pipelined": (C.c_int, [_P, C.c_uint32, C.c_int, _F]),
     "gsh_acq_compute_threshold": (C.c_float, [C.c_float, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "gsh_tlm_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "gsh_tlm_destroy": (None, [_P]),
+    "gsh_tlm_channel_reset": (C.c_int, [_P, C.c_int]),
+    "gsh_tlm_check_jobs": (C.c_int, [C.c_int, C.c_uint64, C.POINTER(TlmPageJob), C.c_int]),
+    "gsh_tlm_preamble_scan": (C.c_int, [_P, C.c_int, _F, C.c_uint64, _I8]),
+    "gsh_tlm_decode_pages": (C.c_int, [_P, _F, C.c_uint64, C.POINTER(TlmPageJob), C.c_int, C.POINTER(TlmPageResult)]),
+    "gsh_tlm_decode_pages_device": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(TlmPageJob), C.c_int, C.POINTER(TlmPageResult)]),
+    "gsh_tlm_time_decode_pages": (C.c_int, [_P, _F, C.c_uint64, C.POINTER(TlmPageJob), C.c_int, C.c_int, _F]),
 }
 
 _lib = None

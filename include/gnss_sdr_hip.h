@@ -1399,6 +1399,60 @@ extern "C"
     /* compute_threshold, acq.cc:52-56: 2*gamma_p_inv(2*max_dwells, (1-pfa)^(1/(effective*bins))) */
     float gsh_acq_compute_threshold(float pfa, uint32_t effective_fft_size, uint32_t num_doppler_bins, uint32_t max_dwells);
 
+    /* ---- Galileo telemetry pages (I/NAV on E1B / E5b, F/NAV on E5a, C/NAV on E6) ------------------------------------------------
+     * The page decoder of galileo_telemetry_decoder_gs (src/algorithms/telemetry_decoder/gnuradio_blocks/galileo_telemetry_decoder_gs.cc):
+     * deinterleaver (:352-361), the NOT gate of G2 (:371-377), Viterbi_Decoder::decode (libs/viterbi_decoder.cc:47-120; K = 7, rate 1/2,
+     * generators 121 / 91), CRC-24Q (boost::crc_optimal<24, 0x1864CFBU, 0, 0, false, false> of galileo_{inav,fnav,cnav}_message.cc), and the
+     * clipped preamble correlation of the frame synchroniser (:962-972).  The symbols are the p_data_accu[0] of the gsh_trk_epoch records
+     * whose symbol_flags bit 0 is set.  Page contents are not decoded here.
+     * metric_mode GSH_TLM_METRIC_FULL: both symbols of a pair enter the branch metric and every page starts from state 0 alone -- a
+     * maximum-likelihood decoder.  GSH_TLM_METRIC_REFERENCE: the reference as it runs -- only the first symbol of each pair enters
+     * (viterbi_decoder.cc:61 copies d_nn - 1 elements) and, but for element 0 (:56), a page starts from the metrics the channel's previous
+     * page ended with; those 64 floats per channel live in the handle between pages and launches.  |symbol| <= 1e5 in that mode. */
+#define GSH_TLM_METRIC_FULL 0
+#define GSH_TLM_METRIC_REFERENCE 1
+#define GSH_TLM_MAX_CHANNELS 65536
+#define GSH_TLM_JOB_INVERT 1u       /* negate every symbol: the 180 deg lock, galileo_telemetry_decoder_gs.cc:1040-1046 */
+#define GSH_TLM_JOB_CRC_CONTINUE 2u /* the CRC register continues from this channel's previous job instead of starting at zero */
+#define GSH_TLM_JOB_INAV_AUTO 4u    /* frame type 1 only: the page's first bit chooses the CRC work (galileo_inav_message.cc:146-177) -- 0, an even
+                                       part: register from zero, 114 bits, no comparison; 1, an odd part: continue, 82 bits, compare.  crc_bits,
+                                       crc_check and GSH_TLM_JOB_CRC_CONTINUE of the job are then ignored */
+    typedef struct gsh_tlm gsh_tlm_t;
+    typedef struct
+    {
+        int32_t channel;
+        int32_t frame_type;     /* d_frame_type: 1 I/NAV page part (240 symbols, 114 bits), 2 F/NAV (488, 238), 3 C/NAV (984, 486) */
+        uint64_t symbol_offset; /* the first symbol after the preamble */
+        uint32_t flags;         /* GSH_TLM_JOB_* */
+        int32_t crc_bits;       /* bits fed to the CRC from the page's first, 0 for none */
+        int32_t crc_check;      /* nonzero: compare the 24 bits that follow with the register */
+        int32_t reserved;
+    } gsh_tlm_page_job; /* 32 bytes */
+    typedef struct
+    {
+        uint32_t bits[16];     /* the information bits, MSB first: bit t is bit 31 - t % 32 of word t / 32; the rest is 0 */
+        uint32_t crc_register; /* after crc_bits bits */
+        int32_t crc_ok;        /* 1 / 0, or -1 when nothing was compared */
+    } gsh_tlm_page_result; /* 72 bytes */
+    int gsh_tlm_create(int device, int n_channels, int metric_mode, gsh_tlm_t** out);
+    void gsh_tlm_destroy(gsh_tlm_t* h);
+    /* a fresh Viterbi_Decoder and a CRC register of zero for one channel (what a new telemetry block starts with) */
+    int gsh_tlm_channel_reset(gsh_tlm_t* h, int channel);
+    /* the range checks of a job table, on the host alone: GSH_ERR_INVALID for a window that leaves the n_symbols of the buffer, an unknown
+     * frame type or flag, a channel >= n_channels, crc_bits (+ 24 with crc_check) beyond the page.  The decode entry points run it before any launch */
+    int gsh_tlm_check_jobs(int n_channels, uint64_t n_symbols, const gsh_tlm_page_job* jobs, int n_jobs);
+    /* galileo_telemetry_decoder_gs.cc:962-972 at every position of a block of n host symbols: corr_out[i] = sum_k pre[k] * (symbols[i + k] < 0 ? -1 : +1)
+     * for the preamble of frame_type (10, 12 or 16 symbols); the positions whose window leaves the block, i > n - length, receive 0 */
+    int gsh_tlm_preamble_scan(gsh_tlm_t* h, int frame_type, const float* symbols, uint64_t n, int8_t* corr_out);
+    /* decode_INAV_word / decode_FNAV_word / decode_CNAV_word up to the CRC verdict (:364-560) for every job of the table.  Jobs of one channel are
+     * taken in table order, channels may interleave in any way.  symbols: n_symbols host floats; jobs and results: host arrays of n_jobs */
+    int gsh_tlm_decode_pages(gsh_tlm_t* h, const float* symbols, uint64_t n_symbols, const gsh_tlm_page_job* jobs, int n_jobs, gsh_tlm_page_result* results);
+    /* the same over n_symbols floats resident on the handle's device (borrowed for the call) */
+    int gsh_tlm_decode_pages_device(gsh_tlm_t* h, const void* device_symbols, uint64_t n_symbols, const gsh_tlm_page_job* jobs, int n_jobs,
+        gsh_tlm_page_result* results);
+    /* HIP-event average milliseconds per launch of the job table, inputs resident (the carried state of the channels moves on) */
+    int gsh_tlm_time_decode_pages(gsh_tlm_t* h, const float* symbols, uint64_t n_symbols, const gsh_tlm_page_job* jobs, int n_jobs, int reps, float* avg_ms);
+
 #ifdef __cplusplus
 }
 #endif
