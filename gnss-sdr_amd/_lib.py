@@ -308,6 +308,62 @@ class TlmPageResult(C.Structure):
     ]
 
 
+class CnavJob(C.Structure):
+    """gsh_cnav_job (32 bytes)."""
+    _fields_ = [
+        ("channel", C.c_int32),
+        ("reserved", C.c_int32),
+        ("symbol_offset", C.c_uint64),
+        ("n_symbols", C.c_uint64),
+        ("result_offset", C.c_uint32),
+        ("result_capacity", C.c_uint32),
+    ]
+
+
+class CnavMessage(C.Structure):
+    """gsh_cnav_message (60 bytes)."""
+    _fields_ = [
+        ("bits", C.c_uint32 * 10),
+        ("symbol_index", C.c_uint32),
+        ("delay", C.c_uint32),
+        ("tow", C.c_uint32),
+        ("prn", C.c_uint8),
+        ("msg_id", C.c_uint8),
+        ("alert", C.c_uint8),
+        ("part", C.c_uint8),
+        ("invert", C.c_uint8),
+        ("invert_or", C.c_uint8),
+        ("reserved", C.c_uint8 * 2),
+    ]
+
+
+class CnavPartState(C.Structure):
+    """gsh_cnav_part_state (1240 bytes)."""
+    _fields_ = [
+        ("decisions", C.c_uint64 * 64),
+        ("old_metrics", C.c_uint32 * 64),
+        ("new_metrics", C.c_uint32 * 64),
+        ("symbols", C.c_uint8 * 128),
+        ("decoded", C.c_uint32 * 16),
+        ("decisions_index", C.c_uint32),
+        ("n_symbols", C.c_uint32),
+        ("n_decoded", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("n_crc_fail", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class CnavChannelState(C.Structure):
+    """gsh_cnav_channel_state (2480 bytes)."""
+    _fields_ = [("part", CnavPartState * 2)]
+
+
+GSH_CNAV_QUANTISER_HARD = 0
+GSH_CNAV_QUANTISER_SOFT = 1
+GSH_CNAV_FLAG_PREAMBLE_SEEN, GSH_CNAV_FLAG_INVERT, GSH_CNAV_FLAG_MESSAGE_LOCK, GSH_CNAV_FLAG_CRC_OK, GSH_CNAV_FLAG_INIT = 1, 2, 4, 8, 16
+
+
 class AcqResult(C.Structure):
     """gsh_acq_result."""
     _fields_ = [
@@ -547,6 +603,17 @@ SYMBOLS = {
     "gsh_tlm_decode_pages": (C.c_int, [_P, _F, C.c_uint64, C.POINTER(TlmPageJob), C.c_int, C.POINTER(TlmPageResult)]),
     "gsh_tlm_decode_pages_device": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(TlmPageJob), C.c_int, C.POINTER(TlmPageResult)]),
     "gsh_tlm_time_decode_pages": (C.c_int, [_P, _F, C.c_uint64, C.POINTER(TlmPageJob), C.c_int, C.c_int, _F]),
+    "gsh_cnav_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(_P)]),
+    "gsh_cnav_destroy": (None, [_P]),
+    "gsh_cnav_channel_reset": (C.c_int, [_P, C.c_int]),
+    "gsh_cnav_check_jobs": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(CnavJob), C.c_int]),
+    "gsh_cnav_push_u8": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(CnavJob), C.c_int, C.POINTER(CnavMessage), C.c_uint32,
+                                   C.POINTER(C.c_int32)]),
+    "gsh_cnav_push_f32": (C.c_int, [_P, _F, C.c_uint64, C.POINTER(CnavJob), C.c_int, C.POINTER(CnavMessage), C.c_uint32, C.POINTER(C.c_int32)]),
+    "gsh_cnav_push_f32_device": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(CnavJob), C.c_int, C.POINTER(CnavMessage), C.c_uint32, C.POINTER(C.c_int32)]),
+    "gsh_cnav_time_push": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(CnavJob), C.c_int, C.c_int, _F]),
+    "gsh_cnav_channel_get_state": (C.c_int, [_P, C.c_int, C.POINTER(CnavChannelState)]),
+    "gsh_cnav_channel_set_state": (C.c_int, [_P, C.c_int, C.POINTER(CnavChannelState)]),
 }
 
 _lib = None

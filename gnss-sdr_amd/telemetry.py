@@ -1,11 +1,14 @@
-"""Galileo telemetry pages: the ctypes face of gsh_tlm_* (csrc/telemetry_viterbi.hip) and the frame synchroniser of galileo_telemetry_decoder_gs
-restated on the host over device results.
+"""Telemetry on the device.  Galileo pages: the ctypes face of gsh_tlm_* (csrc/telemetry_viterbi.hip) and the frame synchroniser of
+galileo_telemetry_decoder_gs restated on the host over device results.  GPS CNAV messages (L2C, L5): the ctypes face of gsh_cnav_*
+(csrc/cnav_stream.hip), libswiftcnav's streaming decoder with its state kept on the device.
 
   symbols_from_records   the telemetry symbols of one channel's gsh_trk_epoch records
   TelemetryDecoder       one gsh_tlm handle: preamble scan and page-job tables on the device
   GalileoFrameSync       galileo_telemetry_decoder_gs.cc:953-1110: preamble search, lock, one page per period, loss of lock after 7 CRC failures
+  CnavDecoder            one gsh_cnav handle: n channels of cnav_msg_decoder_add_symbol, as gps_l2c / gps_l5_telemetry_decoder_gs drive it
 
-Not here: the contents of the pages (ephemeris, TOW, HAS, OSNMA, Reed-Solomon), a TelemetryDecoderInterface adapter, GPS CNAV and SBAS (other decoders).
+Not here: the contents of the pages and messages (ephemeris, TOW, HAS, OSNMA, Reed-Solomon, Gps_CNAV_Navigation_Message), a TelemetryDecoderInterface
+adapter, GPS L1 C/A LNAV and SBAS (other decoders).
 """
 from __future__ import annotations
 
@@ -15,6 +18,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._lib import (GSH_CNAV_QUANTISER_HARD, GSH_CNAV_QUANTISER_SOFT, CnavChannelState, CnavJob, CnavMessage)
 from ._lib import (GSH_TLM_JOB_INAV_AUTO, GSH_TLM_JOB_INVERT, GSH_TLM_METRIC_FULL, GSH_TLM_METRIC_REFERENCE, TlmPageJob, TlmPageResult, check, fptr)
 
 CRC_ERROR_LIMIT = 6  # galileo_telemetry_decoder_gs.cc:70
@@ -27,11 +31,12 @@ FRAME = {
 _METRIC = {"full": GSH_TLM_METRIC_FULL, "reference": GSH_TLM_METRIC_REFERENCE}
 
 
-def symbols_from_records(records):
-    """-> (symbols float32, sample_counters uint64) of one channel's gsh_trk_epoch records: p_data_accu[0] of every record whose symbol_flags bit 0
-    is set (a telemetry symbol was completed in that epoch), in order"""
+def symbols_from_records(records, component=0):
+    """-> (symbols float32, sample_counters uint64) of one channel's gsh_trk_epoch records: p_data_accu[component] of every record whose symbol_flags
+    bit 0 is set (a telemetry symbol was completed in that epoch), in order.  component 0 is Prompt_I (Galileo, GPS L2C), 1 is Prompt_Q, which the
+    GPS L5 block reads (gps_l5_telemetry_decoder_gs.cc:213)"""
     keep = [r for r in records if r.symbol_flags & 1]
-    return (np.array([r.p_data_accu[0] for r in keep], np.float32), np.array([r.sample_counter for r in keep], np.uint64))
+    return (np.array([r.p_data_accu[component] for r in keep], np.float32), np.array([r.sample_counter for r in keep], np.uint64))
 
 
 def unpack_bits(words, info_bits: int):
@@ -246,3 +251,138 @@ class GalileoFrameSync:
             drop = min(max(keep - c.base, 0), len(c.buf))
             c.buf, c.base = c.buf[drop:], c.base + drop
         return pages
+
+
+@dataclass
+class CnavMessageOut:
+    channel: int
+    symbol_index: int  # counted from the channel's first pushed symbol: the symbol that completed the message
+    bits: np.ndarray   # uint8, the 300 bits, un-inverted
+    words: np.ndarray  # uint32, the same MSB first in 10 words
+    delay: int         # cnav_msg.c:344, in symbols
+    prn: int
+    msg_id: int
+    tow: int           # in 6 s units
+    alert: bool
+    part: int          # 1 or 2: which of the two decoders delivered
+    invert: bool       # that part's invert flag
+    phase_locked_180: bool  # part1.invert | part2.invert: d_flag_PLL_180_deg_phase_locked of both blocks (gps_l5_telemetry_decoder_gs.cc:227-234)
+    time_of_symbol: float   # the block's time of the current symbol: seconds for L2C, milliseconds for L5
+
+
+def cnav_result_capacity(n_symbols: int) -> int:
+    """GSH_CNAV_RESULT_CAPACITY: the messages n symbols can deliver (576 symbols apart at the closest)"""
+    return 1 if n_symbols == 0 else (n_symbols + 575) // 576
+
+
+def cnav_job_table(jobs):
+    """list of dicts (channel, symbol_offset, n_symbols, result_offset, result_capacity) -> gsh_cnav_job array"""
+    table = (CnavJob * max(1, len(jobs)))()
+    for t, j in zip(table, jobs):
+        t.channel, t.symbol_offset, t.n_symbols = int(j["channel"]), int(j["symbol_offset"]), int(j["n_symbols"])
+        t.result_offset, t.result_capacity = int(j["result_offset"]), int(j["result_capacity"])
+    return table
+
+
+class CnavDecoder:
+    """gsh_cnav_*: n_channels GPS CNAV message decoders on one device, each the pair of sliding-window Viterbi decoders and message-lock machines of
+    libswiftcnav's cnav_msg_decoder_t, kept on the device from push to push.  signal "L2C" or "L5" only chooses the block's time formula; quantiser
+    "hard" is what both blocks do ((x > 0) * 255), ("soft", scale) maps [-scale, scale] onto 0..255."""
+
+    def __init__(self, n_channels: int, signal: str = "L2C", quantiser="hard", device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        if signal not in ("L2C", "L5"):
+            raise ValueError(f"unknown signal {signal!r}")
+        if quantiser == "hard":
+            mode, scale = GSH_CNAV_QUANTISER_HARD, 1.0
+        elif isinstance(quantiser, tuple) and len(quantiser) == 2 and quantiser[0] == "soft":
+            mode, scale = GSH_CNAV_QUANTISER_SOFT, float(quantiser[1])
+        else:
+            raise ValueError(f"unknown quantiser {quantiser!r}")
+        self.n_channels, self.signal, self.quantiser = n_channels, signal, quantiser
+        self.pushed = [0] * n_channels  # symbols each channel has taken since its reset
+        check(self._lib.gsh_cnav_create(device, n_channels, mode, scale, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._lib.gsh_cnav_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+    def channel_reset(self, channel: int):
+        check(self._lib.gsh_cnav_channel_reset(self._h, channel))
+        self.pushed[channel] = 0
+
+    def get_state(self, channel: int) -> CnavChannelState:
+        state = CnavChannelState()
+        check(self._lib.gsh_cnav_channel_get_state(self._h, channel, C.byref(state)))
+        return state
+
+    def set_state(self, channel: int, state: CnavChannelState, pushed: int = 0):
+        """puts a whole decoder state into a channel; `pushed` is the symbol count the channel's later indices continue from"""
+        check(self._lib.gsh_cnav_channel_set_state(self._h, channel, C.byref(state)))
+        self.pushed[channel] = pushed
+
+    def time_of_symbol(self, tow: int, delay: int) -> float:
+        if self.signal == "L2C":
+            return tow * 6 + delay * 0.02 + 12 * 0.02  # gps_l2c_telemetry_decoder_gs.cc:287, seconds
+        return float(tow * 6000 + (delay + 12) * 10)   # gps_l5_telemetry_decoder_gs.cc:308, milliseconds
+
+    def _layout(self, blocks, dtype):
+        chans = list(blocks)
+        arrays = [np.ascontiguousarray(blocks[c], dtype).reshape(-1) for c in chans]
+        jobs, at, res = [], 0, 0
+        for c, a in zip(chans, arrays):
+            cap = cnav_result_capacity(len(a))
+            jobs.append(dict(channel=c, symbol_offset=at, n_symbols=len(a), result_offset=res, result_capacity=cap))
+            at, res = at + len(a), res + cap
+        return jobs, (np.concatenate(arrays) if arrays else np.zeros(0, dtype)), res
+
+    def _collect(self, jobs, table, counts):
+        out = []
+        for j, n in zip(jobs, counts):
+            c = j["channel"]
+            for r in table[j["result_offset"]:j["result_offset"] + n]:
+                words = np.array(r.bits[:], np.uint32)
+                out.append(CnavMessageOut(c, self.pushed[c] + int(r.symbol_index), np.unpackbits(words.astype(">u4").view(np.uint8))[:300], words,
+                                          int(r.delay), int(r.prn), int(r.msg_id), int(r.tow), bool(r.alert), int(r.part), bool(r.invert),
+                                          bool(r.invert_or), self.time_of_symbol(int(r.tow), int(r.delay))))
+            self.pushed[c] += j["n_symbols"]
+        return out
+
+    def push_jobs(self, entry, symbols_arg, n_symbols, jobs, n_results):
+        """one launch over a job table (list of dicts, see cnav_job_table) -> list of CnavMessageOut, per job in table order.  GshError
+        (GSH_ERR_STATE) if a channel delivered more than its job's capacity, which only an imported state can cause"""
+        table = (CnavMessage * max(1, n_results))()
+        counts = (C.c_int32 * max(1, len(jobs)))()
+        check(entry(self._h, symbols_arg, n_symbols, cnav_job_table(jobs), len(jobs), table, n_results, counts))
+        return self._collect(jobs, table, list(counts)[:len(jobs)])
+
+    def push(self, blocks):
+        """blocks: {channel: float symbols, appended to the channel's stream}, through the quantiser -> list of CnavMessageOut"""
+        jobs, x, n_results = self._layout(blocks, np.float32)
+        return self.push_jobs(self._lib.gsh_cnav_push_f32, fptr(x), len(x), jobs, n_results)
+
+    def push_u8(self, blocks):
+        """the same over symbols as the library takes them: uint8, 0x00 a certain 0, 0xFF a certain 1"""
+        jobs, x, n_results = self._layout(blocks, np.uint8)
+        return self.push_jobs(self._lib.gsh_cnav_push_u8, x.ctypes.data_as(C.POINTER(C.c_uint8)), len(x), jobs, n_results)
+
+    def push_device(self, device_ptr: int, n_symbols: int, spans):
+        """spans: {channel: (offset, count)} into n_symbols float32 resident on the decoder's device (e.g. a torch tensor's data_ptr())"""
+        jobs, res = [], 0
+        for c, (offset, count) in spans.items():
+            cap = cnav_result_capacity(count)
+            jobs.append(dict(channel=c, symbol_offset=offset, n_symbols=count, result_offset=res, result_capacity=cap))
+            res += cap
+        return self.push_jobs(self._lib.gsh_cnav_push_f32_device, C.c_void_p(device_ptr), n_symbols, jobs, res)
+
+    def time_push(self, blocks, reps: int = 10) -> float:
+        """HIP-event average milliseconds per launch of uint8 blocks; the channels' states are as before afterwards"""
+        jobs, x, _ = self._layout(blocks, np.uint8)
+        ms = C.c_float()
+        check(self._lib.gsh_cnav_time_push(self._h, x.ctypes.data_as(C.POINTER(C.c_uint8)), len(x), cnav_job_table(jobs), len(jobs), reps, C.byref(ms)))
+        return float(ms.value)

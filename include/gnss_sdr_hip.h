@@ -1453,6 +1453,97 @@ extern "C"
     /* HIP-event average milliseconds per launch of the job table, inputs resident (the carried state of the channels moves on) */
     int gsh_tlm_time_decode_pages(gsh_tlm_t* h, const float* symbols, uint64_t n_symbols, const gsh_tlm_page_job* jobs, int n_jobs, int reps, float* avg_ms);
 
+    /* ---- GPS CNAV messages (L2C, L5) ---------------------------------------------------------------------------------------------
+     * libswiftcnav's streaming decoder (src/algorithms/telemetry_decoder/libs/libswiftcnav/cnav_msg.c, viterbi27.c, bits.c, edc.c) as the
+     * blocks gps_l2c_telemetry_decoder_gs and gps_l5_telemetry_decoder_gs drive it: per channel two sliding-window K = 7 rate 1/2 Viterbi
+     * decoders one symbol apart with integer metrics, each with its message-lock machine (preamble 0x8B or its inverse, 300 bits, CRC-24Q
+     * over 276).  State lives in the handle from symbol to symbol; results equal the reference bit for bit on every input.  The symbols are
+     * the p_data_accu[0] (L2C, Prompt_I) or p_data_accu[1] (L5, Prompt_Q) of the gsh_trk_epoch records whose symbol_flags bit 0 is set.
+     * Message contents beyond prn, msg_id, tow and alert are not decoded here. */
+#define GSH_CNAV_MAX_CHANNELS 65536
+#define GSH_CNAV_QUANTISER_HARD 0 /* (x > 0) * 255: gps_l2c_telemetry_decoder_gs.cc:178, gps_l5_telemetry_decoder_gs.cc:213 */
+#define GSH_CNAV_QUANTISER_SOFT 1 /* rint(127.5 + 127.5 * clamp(x / soft_scale, -1, 1)) in float32: the soft input the library accepts */
+#define GSH_CNAV_FLAG_PREAMBLE_SEEN 1u /* cnav_v27_part_t, cnav_msg.h:78-86 */
+#define GSH_CNAV_FLAG_INVERT 2u
+#define GSH_CNAV_FLAG_MESSAGE_LOCK 4u
+#define GSH_CNAV_FLAG_CRC_OK 8u
+#define GSH_CNAV_FLAG_INIT 16u
+    /* the messages n symbols can deliver: the locked decoder releases 32 bits per 64 symbols and holds fewer than 300 between symbols, so two
+     * messages can complete within 577 symbols, three within 1 153, and so on, 576 apart at the closest (never below n / 600 + 1) */
+#define GSH_CNAV_RESULT_CAPACITY(n) ((n) == 0 ? 1u : ((n) + 575u) / 576u)
+    typedef struct gsh_cnav gsh_cnav_t;
+    typedef struct
+    {
+        uint64_t decisions[64];   /* the decision ring: bit n of an entry is new state n's decision (v27_decision_t.w[0] | w[1] << 32) */
+        uint32_t old_metrics[64]; /* what v27_t.old_metrics points at: the metrics after the last step */
+        uint32_t new_metrics[64]; /* what v27_t.new_metrics points at: those of the step before, which the trace-back ranks */
+        uint8_t symbols[128];     /* cnav_v27_part_t.symbols */
+        uint32_t decoded[16];     /* cnav_v27_part_t.decoded, MSB first: byte b is bits 31 - 8 * (b % 4) .. of word b / 4 */
+        uint32_t decisions_index;
+        uint32_t n_symbols;
+        uint32_t n_decoded;
+        uint32_t flags; /* GSH_CNAV_FLAG_* */
+        uint32_t n_crc_fail;
+        uint32_t reserved;
+    } gsh_cnav_part_state; /* 1240 bytes */
+    typedef struct
+    {
+        gsh_cnav_part_state part[2]; /* part1, part2 of cnav_msg_decoder_t */
+    } gsh_cnav_channel_state; /* 2480 bytes */
+    typedef struct
+    {
+        int32_t channel;
+        int32_t reserved;
+        uint64_t symbol_offset;   /* the channel's new symbols in the call's symbol array */
+        uint64_t n_symbols;       /* at most 2^31 */
+        uint32_t result_offset;   /* the job's slice of the call's result array */
+        uint32_t result_capacity; /* at least GSH_CNAV_RESULT_CAPACITY(n_symbols) */
+    } gsh_cnav_job; /* 32 bytes */
+    typedef struct
+    {
+        uint32_t bits[10];     /* the 300 bits, un-inverted, MSB first; the last 20 bits of word 9 are 0 */
+        uint32_t symbol_index; /* within the job's span, of the symbol that completed the message */
+        uint32_t delay;        /* cnav_msg.c:344: (n_decoded - 300 + 32) * 2 + n_symbols */
+        uint32_t tow;          /* bits 20-36 */
+        uint8_t prn;           /* bits 8-13 */
+        uint8_t msg_id;        /* bits 14-19 */
+        uint8_t alert;         /* bit 37 */
+        uint8_t part;          /* 1 or 2: which part delivered */
+        uint8_t invert;        /* that part's invert flag */
+        uint8_t invert_or;     /* part1.invert | part2.invert, from which both blocks set d_flag_PLL_180_deg_phase_locked
+                                  (gps_l5_telemetry_decoder_gs.cc:227-234); the idle part's flag can be stale */
+        uint8_t reserved[2];
+    } gsh_cnav_message; /* 60 bytes */
+    /* n_channels decoders, each as after cnav_msg_decoder_init (cnav_msg.c:374-390).  soft_scale > 0 is used by GSH_CNAV_QUANTISER_SOFT only */
+    int gsh_cnav_create(int device, int n_channels, int quantiser_mode, float soft_scale, gsh_cnav_t** out);
+    void gsh_cnav_destroy(gsh_cnav_t* h);
+    /* a fresh cnav_msg_decoder_init for one channel */
+    int gsh_cnav_channel_reset(gsh_cnav_t* h, int channel);
+    /* the range checks of a job table, on the host alone: GSH_ERR_INVALID for a channel outside 0..n_channels - 1, two jobs of one channel, a
+     * symbol span that leaves the n_symbols of the array or exceeds 2^31, a result slice that leaves the n_results of the array or overlaps
+     * another job's, a capacity below GSH_CNAV_RESULT_CAPACITY(n_symbols).  The push entry points run it before any launch */
+    int gsh_cnav_check_jobs(int n_channels, uint64_t n_symbols, uint32_t n_results, const gsh_cnav_job* jobs, int n_jobs);
+    /* cnav_msg_decoder_add_symbol (cnav_msg.c:415-439) for every symbol of every job, symbols as the library takes them (0x00 a certain 0, 0xFF
+     * a certain 1).  results: host array of n_results messages, each job writes counts[job] messages from its result_offset; the rest is untouched.
+     * A channel whose state was imported (gsh_cnav_channel_set_state) with a message's worth of bits already decoded can deliver more than its
+     * capacity: the first result_capacity messages are written, counts[job] holds the number delivered, every channel's state has advanced, and
+     * the call returns GSH_ERR_STATE */
+    int gsh_cnav_push_u8(gsh_cnav_t* h, const uint8_t* symbols, uint64_t n_symbols, const gsh_cnav_job* jobs, int n_jobs, gsh_cnav_message* results,
+        uint32_t n_results, int32_t* counts);
+    /* the same over host floats through the handle's quantiser (gps_l2c_telemetry_decoder_gs.cc:178, gps_l5_telemetry_decoder_gs.cc:213) */
+    int gsh_cnav_push_f32(gsh_cnav_t* h, const float* symbols, uint64_t n_symbols, const gsh_cnav_job* jobs, int n_jobs, gsh_cnav_message* results,
+        uint32_t n_results, int32_t* counts);
+    /* the same over n_symbols floats resident on the handle's device (borrowed for the call) */
+    int gsh_cnav_push_f32_device(gsh_cnav_t* h, const void* device_symbols, uint64_t n_symbols, const gsh_cnav_job* jobs, int n_jobs,
+        gsh_cnav_message* results, uint32_t n_results, int32_t* counts);
+    /* HIP-event average milliseconds per launch of the job table over uint8 symbols; the channels' states are put back before every launch and
+     * at the end, so every repetition does the same work and the handle is left as it was */
+    int gsh_cnav_time_push(gsh_cnav_t* h, const uint8_t* symbols, uint64_t n_symbols, const gsh_cnav_job* jobs, int n_jobs, int reps, float* avg_ms);
+    /* a channel's whole cnav_msg_decoder_t (cnav_msg.h:67-99): moves a channel between handles or devices without losing lock.  set_state
+     * refuses a state whose indices or counts leave their arrays */
+    int gsh_cnav_channel_get_state(gsh_cnav_t* h, int channel, gsh_cnav_channel_state* state);
+    int gsh_cnav_channel_set_state(gsh_cnav_t* h, int channel, const gsh_cnav_channel_state* state);
+
 #ifdef __cplusplus
 }
 #endif
